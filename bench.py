@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- scenes/s of the CenterPoint-Pillars nuScenes hot path on N MI355X (one process per GPU).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--workload W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--workload W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -94,7 +94,12 @@ def main(argv=None):
                     "and the other workloads (profiling runs: only warm-up + timed steps are launched)")
     ap.add_argument("--stub-ops", action="store_true", help="test hook: no device ops, launch / collective path only "
                     "(CPU, gloo); the line is marked stub")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last "
+                    "timed step returned as DIR/out_<i>.npy (float32 / float64, 64 MB at most: larger outputs as a "
+                    "fixed seeded sample; rank 0 only)")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.batch is None:
         args.batch = WORKLOADS[args.workload][1]
     if args.repeats is None:

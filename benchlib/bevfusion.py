@@ -152,7 +152,7 @@ def bench_camera_pool(args, rank, world, dev):
         import copy as _copy
 
         a2 = _copy.copy(args)
-        a2.repeats = 0
+        a2.repeats, a2.dump_outputs = 0, None
         dt_l, ms_l, out_l, _ = _timed_loop(run_lifted, a2, world, dev, ["start", "geometry", "lift", "index_build_and_pool"])
         del out_l
         torch.cuda.empty_cache()

@@ -213,6 +213,8 @@ def _timed_loop(step, args, world, dev, names, finish=None):
         events = _events(names, args.steps, dev)
         dt, out = block(events)
         sync()
+        if getattr(args, "dump_outputs", None) and (world == 1 or torch.distributed.get_rank() == 0):
+            dump_outputs(out, args.dump_outputs)
         per_op_ms = {names[i]: float(np.median([events[k][i - 1].elapsed_time(events[k][i])
                                                 for k in range(args.steps)])) for i in range(1, len(names))}
         with NodeSampler() as sampler:
@@ -342,8 +344,54 @@ def h2d_overlapped(run_batch, flush, host_batches, steps, world, dev):
                      f"(dist.H2DStage) on each of the {world} rank(s); MAX over ranks")
 
 
+DUMP_BYTES = 64_000_000  # --dump-outputs: at most this much in all
+_DUMPED = {}  # what dump_outputs wrote: main() adds it to the line
+
+
+def _flatten(out, name):
+    """(name, array) of every tensor / array / number in a step's output, nested tuples / lists / dicts in order."""
+    if out is None:
+        return []
+    if isinstance(out, dict):
+        return [x for k, v in out.items() for x in _flatten(v, f"{name}_{k}")]
+    if isinstance(out, (list, tuple)):
+        return [x for i, v in enumerate(out) for x in _flatten(v, f"{name}_{i}")]
+    if isinstance(out, torch.Tensor):
+        out = out.detach().cpu()
+        if out.dtype.is_floating_point and out.element_size() < 4:  # (NumPy has no bfloat16)
+            out = out.float()
+        out = out.numpy()
+    a = np.asarray(out)
+    # float64 stays float64; narrower floats widen to float32 exactly; integers / bools as float64 (exact below 2^53)
+    return [(name, a.astype(np.float32 if a.dtype.kind == "f" and a.itemsize <= 4 else np.float64))]
+
+
+def dump_outputs(out, directory):
+    """--dump-outputs DIR: the arrays the last timed step returned as DIR/<name>.npy (float32 / float64), names out_0,
+    out_1, ... in the order the step returns them.  Above DUMP_BYTES in all, every array larger than an even share of
+    the budget is replaced by a fixed sample of its flattened elements (seed 0, ascending index order), so that two
+    builds given the same arguments write comparable files."""
+    arrays = _flatten(out, "out")
+    share = DUMP_BYTES // max(1, len(arrays))
+    total = sum(a.nbytes for _, a in arrays)
+    os.makedirs(directory, exist_ok=True)
+    _DUMPED.clear()
+    _DUMPED.update(dir=directory, arrays={})
+    for name, a in arrays:
+        entry = dict(shape=list(a.shape), dtype=str(a.dtype))
+        if total > DUMP_BYTES and a.nbytes > share:
+            k = share // a.itemsize
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=k, replace=False))
+            entry["sampled"] = f"{k} of {a.size} elements (seed 0, ascending flat index)"
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(directory, name + ".npy"), a)
+        _DUMPED["arrays"][name] = entry
+
+
 def _dist_fields(line, args, world):
     """Fields every workload's line carries about the launch: ranks that took part, spread over repeated blocks."""
+    if _DUMPED:
+        line["dumped_outputs"] = dict(_DUMPED)
     info = _LAST_LOOP
     line["ranks_seen"] = info.get("ranks_seen", 1)
     line["collective_backend"] = (torch.distributed.get_backend() if world > 1 else None)

@@ -55,7 +55,7 @@ def c1_cpu_baseline(frames=2):
     return dict(value=frames / dt, unit="frames/s", cores=torch.get_num_threads(),
                 kind="reference" if kind == "ref" else "port",
                 sample=f"{frames} frames of the same workload: hard_voxelize = "
-                       f"{'reference voxelize_op.cc:19-82 compiled from /root/reference' if kind == 'ref' else 'C port'} "
+                       f"{'reference voxelize_op.cc:19-82 compiled from the reference tree' if kind == 'ref' else 'C port'} "
                        "(1 thread), PFN / SECOND / FPN / head = torch CPU fp32, anchor mask / decode / NMS = NumPy + C port")
 
 

@@ -207,7 +207,7 @@ def cpu_baseline(model_cpu, max_voxels, frames=6):
     for i in range(frames):
         kind = _oracle_scene(model_cpu, max_voxels, 100 + i)
     dt_all = time.perf_counter() - t0
-    src = ("reference voxelize_op.cc:19-82 compiled from /root/reference" if kind == "ref" else "C port")
+    src = ("reference voxelize_op.cc:19-82 compiled from the reference tree" if kind == "ref" else "C port")
     out = dict(value=frames / dt_all, unit="scenes/s", cores=threads, kind="reference" if kind == "ref" else "port",
                sample=f"{frames} frames of the same workload: hard_voxelize = {src} (1 thread), PFN / dense graph = "
                       f"torch CPU fp32 ({threads} threads), scatter / postprocess = C port")
@@ -220,8 +220,9 @@ def cpu_baseline(model_cpu, max_voxels, frames=6):
     finally:
         torch.set_num_threads(threads)
     out["one_thread"] = dict(value=1.0 / dt1, unit="scenes/s", cores=1, sample="1 frame, every stage on 1 thread")
-    # (ii) P processes x 1 thread, one frame each
-    procs = max(1, min(os.cpu_count() or 1, 32))
+    # (ii) P processes x 1 thread, one frame each; P = the threads this job may use (OMP_NUM_THREADS, as torch reads
+    # it), not os.cpu_count(): on a shared node that counts every core of the machine
+    procs = max(1, min(threads, 32))
     try:
         with tempfile.TemporaryDirectory() as tmp:
             path = os.path.join(tmp, "state.pt")
@@ -363,7 +364,7 @@ def bench_pillars(args, rank, world, dev):
         import copy as _copy
 
         a2 = _copy.copy(args)
-        a2.repeats = 0
+        a2.repeats, a2.dump_outputs = 0, None
         fused_front = False  # (compute() reads the flag when it runs)
         # always the EAGER pair step, and BEFORE any graph is captured: eager launches of the step's operators between the
         # replays of a captured graph are what made replays go wrong on this stack (benchlib/graph_selftest.py)

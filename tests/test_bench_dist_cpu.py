@@ -163,3 +163,25 @@ def test_refuses_world_size_mismatch():
     r = _run(["--gpus", "2", "--stub-ops", "--steps", "1", "--warmup", "0"], {"WORLD_SIZE": "1", "RANK": "0"})
     assert r.returncode != 0 and "WORLD_SIZE=1" in (r.stderr + r.stdout)
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
+def test_dump_outputs_of_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR writes what the last timed step returned as float32 / float64 .npy files; with the same
+    arguments the inputs are the same, so two runs write the same arrays whatever --steps is."""
+    import numpy as np
+
+    lines = {}
+    for steps in (2, 5):
+        r = _run(["--stub-ops", "--steps", str(steps), "--warmup", "1", "--batch", "2", "--repeats", "0",
+                  "--dump-outputs", str(tmp_path / f"k{steps}")])
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(out) == 1, r.stdout
+        lines[steps] = json.loads(out[0])
+        assert lines[steps]["steps"] == steps and lines[steps]["ms_per_step"] > 0
+    names = sorted(lines[2]["dumped_outputs"]["arrays"])
+    assert names and names == sorted(lines[5]["dumped_outputs"]["arrays"])
+    for name in names:
+        a, b = np.load(tmp_path / "k2" / f"{name}.npy"), np.load(tmp_path / "k5" / f"{name}.npy")
+        assert a.dtype in (np.float32, np.float64) and a.size > 0
+        np.testing.assert_array_equal(a, b)

@@ -10,6 +10,7 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "golden"))
 import make_ssd_golden as G  # noqa: E402  (case table + seeded input builders; nothing runs at import)
+from recorded_reference import agree_with_reference  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -40,18 +41,28 @@ def test_anchor_restatements(oracle, sg, tag):
 @pytest.mark.parametrize("tag", ["a", "b"])
 @pytest.mark.parametrize("kind", ["port", "ref"])
 def test_post_process_restatement(oracle, sg, tag, kind):
-    if kind == "ref" and not oracle.have_ref():
-        pytest.skip("oracle/_ref not built here")
+    """kind = ref: the restatement with the reference's own NMS (live from oracle/_ref, else its recorded results,
+    tests/golden/recorded_reference.py) gives the same frames as with the port's, bit for bit."""
     c = G.CASES[tag]
     an, bv, _, grid = oracle.ssd_anchors_numpy(c["pcr"], c["vs"], c["anchor_configs"], 2)
     cls, box, dirp = G.head_outputs(tag, c, an.shape[0])
     np.testing.assert_allclose(oracle.ssd_box_decode_numpy(box[0], an), sg[f"{tag}_decoded_0"], rtol=2e-7, atol=1e-6)
     co, h = sg[f"{tag}_coords"], c["head"]
-    for b in range(c["batch"]):
-        mask = oracle.ssd_anchor_mask_numpy(co[co[:, 0] == b][:, 1:], bv, grid, 1.0)
-        bb, ss, ll = oracle.ssd_post_process_frame_numpy(
-            box[b], cls[b], dirp[b], an, mask, h["nms_score_threshold"], h["prediction_center_limit_range"],
-            h["nms_pre_max_size"], h["nms_post_max_size"], h["nms_iou_threshold"], kind=kind)
+
+    def frames(k):
+        out = []
+        for b in range(c["batch"]):
+            mask = oracle.ssd_anchor_mask_numpy(co[co[:, 0] == b][:, 1:], bv, grid, 1.0)
+            out.append(oracle.ssd_post_process_frame_numpy(
+                box[b], cls[b], dirp[b], an, mask, h["nms_score_threshold"], h["prediction_center_limit_range"],
+                h["nms_pre_max_size"], h["nms_post_max_size"], h["nms_iou_threshold"], kind=k))
+        return out
+
+    got = frames("port")
+    if kind == "ref":  # the port's frames are the reference's bit for bit, so the checks below hold for both
+        agree_with_reference(oracle, f"ssd_post_process/{tag}", [a for f in got for a in f],
+                             lambda: [a for f in frames("ref") for a in f])
+    for b, (bb, ss, ll) in enumerate(got):
         np.testing.assert_array_equal(ll, sg[f"{tag}_out_labels_{b}"])
         # exp / sigmoid differ by an ulp between torch (the shim) and NumPy
         np.testing.assert_allclose(bb, sg[f"{tag}_out_boxes_{b}"], rtol=1e-6, atol=4e-6)
