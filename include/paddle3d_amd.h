@@ -317,6 +317,48 @@ int pd3_centerpoint_postprocess_records(const float *const *hm, const float *con
  * reference does; the tests run both and require identical output). */
 
 /* ---------------------------------------------------------------------------------------------
+ * bevdet_postprocess -- BEVDet4D CenterHead post-processing on the device: CenterHeadMatch.get_bboxes
+ * (paddle3d/models/heads/dense_heads/bevdet_centerhead.py:669-783) with CenterPointBBoxCoder.decode (:1119-1214),
+ * Scale-NMS (get_task_detections :785-906, nms_bev :939-968) and circle NMS (:712-739).  All frames and tasks in
+ * one launch sequence (6 launches), no host round trip inside.
+ *
+ *   heatmap/reg/height/dim/rot/vel: host arrays of `num_tasks` device pointers to contiguous fp32 NCHW maps:
+ *     heatmap[t] [batch, task_classes[t], H, W], reg [batch,2,H,W], height [batch,1,H,W], dim [batch,3,H,W],
+ *     rot [batch,2,H,W] (sine, cosine), vel [batch,2,H,W].  H * W <= 2^24, num_tasks <= 16, at most 64 classes.
+ *   nms_type host int[num_tasks] (0 'rotate', 1 'circle'); nms_thr host float[num_tasks] (rotate tasks);
+ *   min_radius host double[num_tasks] (circle tasks: compared with the SQUARED centre distance, as the reference);
+ *   rescale_factors host float[sum(task_classes)]: nms_rescale_factor per class in label order (a scalar factor
+ *     repeated over the task's classes; 1.0 where the reference's list is shorter; rotate tasks only, nonzero).
+ *   max_num: coder top-K, 1..min(1024, H * W) (k > H * W raises in the reference's paddle.topk: PD3_EINVAL;
+ *     1024 < k <= H * W: PD3_EUNSUPPORTED).  pre_max_size / post_max_size >= 1.
+ *   score_threshold: 0 = none (the coder tests `if self.score_threshold:`), else score > threshold.
+ *   post_center_range float[6] (coder), post_center_limit_range float[6] (test_cfg; NULL = no post-NMS mask),
+ *   pc_range float[2], voxel_size float[2], out_size_factor.
+ *   out_bboxes [batch, num_tasks * post_max_size, 9] fp32 (x, y, z of the box bottom, dims, rot, vx, vy)
+ *   out_scores [batch, same rows] fp32; out_labels [batch, same rows] int32 (offset by the earlier tasks' classes)
+ *   out_count  [batch] int32: valid leading rows per frame, tasks in order; rows behind it read zero.
+ */
+size_t pd3_bevdet_postprocess_workspace(int batch, int num_tasks, const int *task_classes, int feat_h, int feat_w,
+                                        int max_num);
+int pd3_bevdet_postprocess(const float *const *heatmap, const float *const *reg, const float *const *height,
+                           const float *const *dim, const float *const *rot, const float *const *vel, int batch,
+                           int num_tasks, const int *task_classes, int feat_h, int feat_w, const int *nms_type,
+                           const float *nms_thr, const double *min_radius, const float *rescale_factors,
+                           int max_num, int pre_max_size, int post_max_size, float score_threshold, int norm_bbox,
+                           const float *post_center_range, const float *post_center_limit_range,
+                           const float *pc_range, const float *voxel_size, float out_size_factor,
+                           float *out_bboxes, float *out_scores, int32_t *out_labels, int32_t *out_count,
+                           void *workspace, size_t workspace_bytes, void *stream);
+
+/* circle_nms (paddle3d/geometries/bbox.py:450-474) on the device.  dets [n, 3] fp32 (x, y, score), device.
+ * Greedy over descending score (equal scores: ascending index); j is suppressed by a kept i when
+ * (x_i - x_j)^2 + (y_i - y_j)^2 (fp32) <= thresh (double).  keep [n] int32 receives the kept indices in order,
+ * num_to_keep [1] int32 their number (both device).  n <= 65536. */
+size_t pd3_circle_nms_workspace(int n);
+int pd3_circle_nms(const float *dets, int n, double thresh, int32_t *keep, int32_t *num_to_keep, void *workspace,
+                   size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * bev_pool_v2 / bev_pool_v2_bkwd -- replace PD_BUILD_OP(bev_pool_v2) (bev_pool_v2/bev_pool.cc:111-118,
  * kernel bev_pool_cuda.cu:18-44) and PD_BUILD_OP(bev_pool_v2_bkwd)
  * (bev_pool_v2_backward/bev_pool_bkwd.cc:75-80, kernel bev_pool_cuda_bkwd.cu:44-94).

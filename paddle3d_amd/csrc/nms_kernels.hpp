@@ -222,10 +222,12 @@ static __global__ __launch_bounds__(64) void nms_cand_kernel(const int* __restri
 static __global__ __launch_bounds__(256) void nms_pairs_kernel(const BoxPre* __restrict__ pre,
                                                                const int* __restrict__ counts, int sets, int cap,
                                                                int cb_cap, float thresh,
-                                                               unsigned long long* __restrict__ mask, NmsPool pl) {
+                                                               unsigned long long* __restrict__ mask, NmsPool pl,
+                                                               const float* __restrict__ set_thresh = nullptr) {
   __shared__ float poly_s[4 * kPolyWaveFloats];
   float* st = poly_s + wave_id() * kPolyWaveFloats + lane_id();
   const int set = blockIdx.y;
+  if (set_thresh) thresh = set_thresh[set];  // one IoU threshold per set (BEVDet's per-task nms_thr)
   const BoxPre* ps = pre + (int64_t)set * cap;
   unsigned long long* ms = mask + (int64_t)set * cap * cb_cap;
   const int total = min(pl.counts[set * kNmsCtrStride], pl.per_set);
@@ -257,10 +259,12 @@ static __global__ __launch_bounds__(256) void nms_pairs_kernel(const BoxPre* __r
 }
 
 // The rotated-box bit matrix of `sets` sets (counts on the device): candidate pass, then the pooled pairs.
+// `set_thresh` (optional, device [sets]) replaces `thresh` per set.
 static inline void nms_enqueue_mask_pooled(const BoxPre* pre, const int* counts, int sets, int cap, int cb, float thresh,
-                                           unsigned long long* mask, const NmsPool& pl, hipStream_t s) {
+                                           unsigned long long* mask, const NmsPool& pl, hipStream_t s,
+                                           const float* set_thresh = nullptr) {
   nms_cand_kernel<<<dim3(cb * (cb + 1) / 2, sets), 64, 0, s>>>(counts, sets, cap, cb, mask, pl);
-  nms_pairs_kernel<<<dim3(kNmsPairWgs, sets), 256, 0, s>>>(pre, counts, sets, cap, cb, thresh, mask, pl);
+  nms_pairs_kernel<<<dim3(kNmsPairWgs, sets), 256, 0, s>>>(pre, counts, sets, cap, cb, thresh, mask, pl, set_thresh);
 }
 
 // One workgroup per set.  keep [set][cap] receives kept indices in order; num_keep[set] their number.
