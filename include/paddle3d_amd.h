@@ -359,6 +359,34 @@ int pd3_circle_nms(const float *dets, int n, double thresh, int32_t *keep, int32
                    size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * bevdet4d_align -- BEVDet4D temporal alignment: BEVDet4D.shift_feature for every adjacent frame and the channel
+ * concat of its callers (paddle3d/models/detection/bevdet/bevdet4d.py:90-159, extract_img_feat_sequential
+ * :194-216, extract_img_feat :291-298) in one launch, no host round trip.  fp32 only.
+ *
+ *   feats: host array of `num_frame` device pointers; feats[0] is the current frame (copied bit for bit), feats[1..]
+ *     the adjacent frames.  Each is [batch, channels, feat_h, feat_w] with the element strides
+ *     strides[4*f .. 4*f+3] = (n, c, h, w): contiguous NCHW and the channels-last view voxel_pooling_v2 returns are
+ *     both read in place.  num_frame <= 16.  with_current 0: feats[0] is not read and the output holds the adjacent
+ *     frames only (shift_feature itself).
+ *   rots_cur / trans_cur / rots_adj / trans_adj / bda / bda_adj: host arrays of `num_frame - 1` device pointers, one
+ *     per adjacent frame, each at camera 0 of batch entry 0: a [3, 3] rotation, a [3] translation, a [3, 3] bda,
+ *     row-major and contiguous; entry b lies `pose_strides[6*(f-1) + k]` elements further (k = 0..5 in the order of
+ *     the six arrays).  bda_adj NULL (or an entry NULL): bda for both poses.
+ *   grid_interval / grid_lower_bound: host float[2] (x, y) of the view transformer (feat2bev); feat_h, feat_w >= 2.
+ *   out [batch, (num_frame - 1 + with_current) * channels, feat_h, feat_w] contiguous; out_grid
+ *     [(num_frame - 1) * batch, feat_h, feat_w, 2] (adjacent frame major) receives the normalised sampling grid,
+ *     or NULL.
+ *   tf is composed in double (closed-form inverse) and rounded to fp32 once; the per-pixel grid and the bilinear
+ *   sum run in fp32 in the order documented in csrc/bev_shift.hip.  All offsets are 64-bit.
+ */
+int pd3_bevdet4d_align(const float *const *feats, const int64_t *strides, int num_frame, int with_current,
+                       int batch, int channels, int feat_h, int feat_w, const float *const *rots_cur,
+                       const float *const *trans_cur, const float *const *rots_adj, const float *const *trans_adj,
+                       const float *const *bda, const float *const *bda_adj, const int64_t *pose_strides,
+                       const float *grid_interval, const float *grid_lower_bound, float *out, float *out_grid,
+                       void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * bev_pool_v2 / bev_pool_v2_bkwd -- replace PD_BUILD_OP(bev_pool_v2) (bev_pool_v2/bev_pool.cc:111-118,
  * kernel bev_pool_cuda.cu:18-44) and PD_BUILD_OP(bev_pool_v2_bkwd)
  * (bev_pool_v2_backward/bev_pool_bkwd.cc:75-80, kernel bev_pool_cuda_bkwd.cu:44-94).
