@@ -7,7 +7,7 @@
 //
 // A "set" is one (frame, task): set = frame * num_tasks + task.  Launches for the whole batch:
 //   1. bd_select_decode_kernel  one 1024-thread workgroup per set: sigmoid keys of all ncls * H * W (class, cell)
-//      entries, exact top-max_num selection (radix select + ordered compaction + bitonic sort), decode of the
+//      entries, exact top-max_num selection (block_topk.hpp), decode of the
 //      selected entries only, score / centre masks, order-keeping compaction; lays out the NMS input of the set
 //   2. nms_cand_kernel + nms_pairs_kernel (nms_kernels.hpp): rotated-IoU bit matrix of the 'rotate' sets, with
 //      the set's own nms_thr
@@ -31,6 +31,7 @@
 // the conversion nms_bev and rotate_nms_pcdet each apply once; Scale-NMS dims d * f for the IoU and (d * f) / f in
 // the output; circle distance fp32 with each square rounded, compared with min_radius in double.
 #include "../../include/paddle3d_amd.h"
+#include "block_topk.hpp"
 #include "common.hpp"
 #include "nms_kernels.hpp"
 #include "radix_sort.hpp"
@@ -42,9 +43,6 @@ namespace pd3 {
 
 constexpr int kBdMaxTasks = 16;
 constexpr int kBdMaxClasses = 64;   // classes of all tasks together (rescale factors)
-constexpr int kBdThreads = 1024;
-constexpr int kBdMaxK = 1024;       // sorted list of the selection
-constexpr int kBdCopies = 8;        // histogram replicas (lane & 7)
 constexpr uint32_t kBdKeyOne = 0x3F800000u;  // bits of 1.0f
 constexpr uint32_t kBdKeyNan = 0x3FFFFFFFu;  // a NaN score sorts after every number
 constexpr int kBdKeyBits = 30;
@@ -98,10 +96,10 @@ __device__ __forceinline__ uint32_t bd_key(float s) {
   return bits <= kBdKeyOne ? kBdKeyOne - bits : kBdKeyNan;  // s in [0, 1]: key in [0, bits(1.0f)]
 }
 
-static __global__ __launch_bounds__(kBdThreads) void bd_select_decode_kernel(BdHeads h, BdCfg c, BdWork w, int sets) {
-  __shared__ int hist[kBdCopies * 1024];
-  __shared__ unsigned long long list[kBdMaxK];
-  __shared__ int scr[48];
+static __global__ __launch_bounds__(kTopkThreads) void bd_select_decode_kernel(BdHeads h, BdCfg c, BdWork w, int sets) {
+  __shared__ int hist[kTopkHistWords];
+  __shared__ unsigned long long list[kTopkMaxK];
+  __shared__ int scr[kTopkScratch];
   const int set = blockIdx.x, t = set % c.num_tasks, frame = set / c.num_tasks;
   const int hw = c.hw, ncls = h.ncls[t], n = ncls * hw;
   const int tid = threadIdx.x;
@@ -109,99 +107,23 @@ static __global__ __launch_bounds__(kBdThreads) void bd_select_decode_kernel(BdH
   // ---- keys of every (class, cell) entry: the same sigmoid expression as cp_best_class ----------------------------
   {
     const float* hm = h.hm[t] + (int64_t)frame * n;
-    for (int i = tid; i < n; i += kBdThreads) keys[i] = bd_key(1.0f / (1.0f + lm::expf(-hm[i])));
+    for (int i = tid; i < n; i += kTopkThreads) keys[i] = bd_key(1.0f / (1.0f + lm::expf(-hm[i])));
   }
-  for (int i = tid; i < kBdMaxK; i += kBdThreads) list[i] = ~0ull;
   if (tid == 0) {  // the pool counters of nms_kernels.hpp: no set-up memset
     w.pool.counts[set * kNmsCtrStride] = 0;
     w.pool.counts[(sets + set) * kNmsCtrStride] = 0;
   }
   __syncthreads();
   const int K = min(c.cap, n);
-  // ---- cut-off key kc and how many entries r with key == kc are taken (lowest flat indices first) -----------------
-  uint32_t kc = 0xFFFFFFFFu;  // > every key: all entries (n == K)
-  int r = 0;
-  if (n > K) {
-    uint32_t prefix = 0;
-    int need = K, hi = kBdKeyBits;
-    while (hi > 0) {
-      const int wd = min(hi, 10), shift = hi - wd;
-      for (int i = tid; i < kBdCopies * 1024; i += kBdThreads) hist[i] = 0;
-      __syncthreads();
-      for (int i = tid; i < n; i += kBdThreads) {
-        const uint32_t k = keys[i];
-        if ((k >> hi) == prefix) atomicAdd(&hist[(tid & (kBdCopies - 1)) * 1024 + ((k >> shift) & ((1u << wd) - 1u))], 1);
-      }
-      __syncthreads();
-      int hh = 0;  // thread tid owns bin tid
-#pragma unroll
-      for (int cp = 0; cp < kBdCopies; ++cp) hh += hist[cp * 1024 + tid];
-      int total;
-      const int cum = block_exclusive_scan<kBdThreads>(hh, scr, total);
-      if (need > cum && need <= cum + hh) {  // exactly one bin holds rank `need`
-        scr[40] = hh;
-        scr[41] = tid;
-        scr[42] = need - cum;
-      }
-      __syncthreads();
-      const int in_bin = scr[40];
-      prefix = (prefix << wd) | (uint32_t)scr[41];
-      need = scr[42];
-      hi = shift;
-      __syncthreads();
-      if (need == in_bin) {  // the whole bin is taken: every key below the next prefix
-        prefix = (prefix + 1u) << hi;
-        need = 0;
-        break;
-      }
-    }
-    kc = prefix;
-    r = need;
-  }
-  // ---- compaction in flat order: thread tid owns [tid * ept, (tid + 1) * ept) ------------------------------------
-  {
-    const int ept = (n + kBdThreads - 1) / kBdThreads;
-    const int c0 = min(tid * ept, n), c1 = min(c0 + ept, n);
-    int nless = 0, neq = 0;
-    for (int i = c0; i < c1; ++i) {
-      const uint32_t k = keys[i];
-      nless += k < kc ? 1 : 0;
-      neq += k == kc ? 1 : 0;
-    }
-    int tot_less, tot_eq;
-    int pl = block_exclusive_scan<kBdThreads>(nless, scr, tot_less);
-    int pe = block_exclusive_scan<kBdThreads>(neq, scr, tot_eq);
-    for (int i = c0; i < c1; ++i) {
-      const uint32_t k = keys[i];
-      if (k < kc) {
-        list[pl++] = ((unsigned long long)k << 32) | (uint32_t)i;
-      } else if (k == kc) {
-        if (pe < r) list[tot_less + pe] = ((unsigned long long)k << 32) | (uint32_t)i;
-        ++pe;
-      }
-    }
-  }
-  __syncthreads();
-  // ---- bitonic sort of the K entries (padding ~0 sorts last) -----------------------------------------------------
-  {
-    int n2 = 64;
-    while (n2 < K) n2 <<= 1;
-    for (int size = 2; size <= n2; size <<= 1) {
-      for (int stride = size >> 1; stride > 0; stride >>= 1) {
-        if (tid < (n2 >> 1)) {
-          const int lo = 2 * tid - (tid & (stride - 1));
-          const int hi = lo + stride;
-          const bool up = (lo & size) == 0;
-          const unsigned long long a = list[lo], b = list[hi];
-          if ((a > b) == up) {
-            list[lo] = b;
-            list[hi] = a;
-          }
-        }
-        __syncthreads();
-      }
-    }
-  }
+  // ---- selection (block_topk.hpp); the keys are read back by other threads, hence the full barrier above ---------
+  const TopkCut cut = n > K ? block_topk_cut(K, kBdKeyBits, hist, scr,
+                                             [&](auto f) {
+                                               for (int i = tid; i < n; i += kTopkThreads) f(keys[i]);
+                                             })
+                            : TopkCut{0xFFFFFFFFu, 0};  // > every key: all entries
+  block_topk_compact(
+      cut, n, [&](int i) { return keys[i]; }, [](int i, int) { return (uint32_t)i; }, list, scr);
+  block_topk_sort(list, K);
   // ---- decode of the r-th best entry (decode :1125-1214) ----------------------------------------------------------
   bool keep = false;
   float bx[9] = {};
@@ -235,7 +157,7 @@ static __global__ __launch_bounds__(kBdThreads) void bd_select_decode_kernel(BdH
     if (c.score_threshold != 0.f) keep = keep && score > c.score_threshold;  // `if self.score_threshold:`
   }
   int total;
-  const int pos = block_exclusive_scan<kBdThreads>(keep ? 1 : 0, scr, total);
+  const int pos = block_exclusive_scan<kTopkThreads>(keep ? 1 : 0, scr, total);
   const int64_t row = (int64_t)set * c.cap + pos;
   const bool circle = h.circle[t] != 0;
   if (keep) {
@@ -487,7 +409,7 @@ extern "C" size_t pd3_bevdet_postprocess_workspace(int batch, int num_tasks, con
                                                    int feat_w, int max_num) {
   int64_t ks;
   int tc;
-  if (!bd_shape_ok(batch, num_tasks, task_classes, feat_h, feat_w, &ks, &tc) || max_num <= 0 || max_num > kBdMaxK)
+  if (!bd_shape_ok(batch, num_tasks, task_classes, feat_h, feat_w, &ks, &tc) || max_num <= 0 || max_num > kTopkMaxK)
     return 0;
   size_t bytes;
   bd_carve(nullptr, batch * num_tasks, ks, max_num, &bytes);
@@ -518,7 +440,7 @@ extern "C" int pd3_bevdet_postprocess(
   }
   if (max_num <= 0 || pre_max_size <= 0 || post_max_size <= 0) return PD3_EINVAL;
   if (max_num > feat_h * feat_w) return PD3_EINVAL;  // paddle.topk(k > H * W) raises in the reference
-  if (max_num > kBdMaxK) return PD3_EUNSUPPORTED;
+  if (max_num > kTopkMaxK) return PD3_EUNSUPPORTED;
   const int sets = batch * num_tasks, cap = max_num, cb = (cap + 63) / 64;
   size_t need;
   BdWork w = bd_carve(workspace, sets, ks, cap, &need);
@@ -567,7 +489,7 @@ extern "C" int pd3_bevdet_postprocess(
   c.use_lim = post_center_limit_range ? 1 : 0;
   for (int k = 0; k < 6 && post_center_limit_range; ++k) c.lim[k] = post_center_limit_range[k];
 
-  bd_select_decode_kernel<<<sets, kBdThreads, 0, s>>>(h, c, w, sets);
+  bd_select_decode_kernel<<<sets, kTopkThreads, 0, s>>>(h, c, w, sets);
   nms_enqueue_mask_pooled(w.pre, w.rot_n, sets, cap, cb, 0.f, w.mask, w.pool, s, w.set_thr);
   bd_circle_mask_kernel<<<dim3(cb, cb, sets), 64, 0, s>>>(w.boxes, 9, w.circ_n, 0, cap, cb, w.set_rad, 0.0, w.mask);
   const hipError_t e = bd_sweep(w.mask, w.nms_n, 0, sets, cap, cb, w.keep, w.nkeep, s);

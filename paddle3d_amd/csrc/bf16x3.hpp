@@ -57,10 +57,6 @@ __device__ __forceinline__ void px_st2(float* base, unsigned bytes, unsigned vof
     __builtin_amdgcn_s_waitcnt(0x0f70 | ((N) & 15) | (((N) >> 4) << 14));        \
     asm volatile("" ::: "memory");                                               \
   } while (0)
-// LDS traffic only; fetches in flight travel across it (a __syncthreads would drain every one of them: a fetch into LDS
-// counts as an LDS store)
-__device__ __forceinline__ void px_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 // Items per workgroup of the persistent kernels: one workgroup per CU at a time walks `ipw` consecutive slots of its XCD
 // lane as one stream, the grid is 8 * ceil(nslots / ipw) workgroups.  Chosen to minimise (rounds of 256 workgroups) x (ipw
 // + the half item a workgroup's unhidden first fetches cost): "as many as fill the CUs once" left 136 workgroups of 16

@@ -88,6 +88,10 @@ static inline unsigned sp_window_grid(long long tiles, int per_win) {
 __device__ __forceinline__ int lane_id() { return threadIdx.x & (kWave - 1); }
 __device__ __forceinline__ int wave_id() { return threadIdx.x >> 6; }
 
+// Block barrier for LDS traffic only: global loads in flight travel across it (a __syncthreads would drain every one of
+// them, and a fetch into LDS counts as an LDS store)
+__device__ __forceinline__ void px_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
 // Inclusive scan of one int across the 64 lanes of a wave.
 __device__ __forceinline__ int wave_inclusive_scan(int v) {
 #pragma unroll

@@ -19,13 +19,12 @@
 // Work is tiny (4.6 MB read per nuScenes frame); the op is launch-latency bound, which is why the
 // launch count (5 for all tasks and frames of a batch) and the absence of syncs are what matter.
 #include "../../include/paddle3d_amd.h"
-#include "bf16x3.hpp"
+#include "block_topk.hpp"
 #include "common.hpp"
 #include "nms_kernels.hpp"
 #include "radix_sort.hpp"
 
 #include <algorithm>
-#include <cstring>
 
 namespace pd3 {
 
@@ -186,34 +185,32 @@ __device__ __forceinline__ void cp_decode_row(const CpCfg& c, int set, int r, in
 // Top-K selection instead of a full sort of the score keys: only the first min(count, nms_pre_max_size) cells of
 // the stable ascending-key order are ever used (postprocess.cu:176-206 sorts the masked scores and slices
 // [:nms_pre_max_size]).  One workgroup per set, everything in LDS, from the head maps to the decoded candidates: the
-// keys of the set's hw cells are COMPUTED into LDS (no key array in memory, no count atomics); a radix SELECT (10-bit
-// LDS histograms over the bits a selected key can have) finds the exact cut-off key and how many cells with that key
-// still fit; the selected cells are compacted in cell order -- their head values are requested at this point -- and
-// sorted as (key, cell) pairs by a bitonic network: the same total order a stable key sort gives; the fetched values
-// move to their rank through LDS and thread r decodes the r-th cell (cp_decode_row).  Writes counts[set], clears the
-// set's NMS counters and writes the rows [set][0 .. K).  Every phase was timed by returning early after it
-// (DESIGN_HISTORY 4.4): the kernel is a chain of latencies, and each comment below names the one it removes.
-constexpr int kTopkThreads = 1024;  // one workgroup per set and nothing else on its CU: the kernel is a chain of
-                                    // dependent passes, so its time is its latency -- 16 waves shorten every pass
+// keys of the set's hw cells are COMPUTED into LDS (no key array in memory, no count atomics); block_topk.hpp selects
+// the cells and sorts them as (key, cell) pairs -- their head values are requested between the compaction and the
+// sort; the fetched values move to their rank through LDS and thread r decodes the r-th cell (cp_decode_row).  Writes
+// counts[set], clears the set's NMS counters and writes the rows [set][0 .. K).  Every phase was timed by returning
+// early after it (DESIGN_HISTORY 4.4): the kernel is a chain of latencies, and each comment below names the one it
+// removes.  kTopkThreads = 1024 threads, one workgroup per set and nothing else on its CU: the kernel is a chain of
+// dependent passes, so its time is its latency -- 16 waves shorten every pass.
 constexpr int kTopkMaxHw = 16384;   // keys held in LDS
-constexpr int kTopkMaxK = 1024;     // bitonic list
 constexpr int kTopkBatch = 4;       // cells of a thread whose keys are computed side by side
-constexpr int kTopkCopies = 8;      // histogram replicas (lane & 7): scores crowd into a handful of exponent bins, and
-                                    // LDS atomics of one wave on one address run one lane at a time
 
 // Where cell i's key sits in LDS: one word of padding per 16 cells, so that the compaction's threads (16 consecutive
 // cells each at 16 k cells) read 64 different banks instead of 4.
 __device__ __forceinline__ int kidx(int i) { return i + (i >> 4); }
+// Words of cp_topk_kernel's key region: the padded keys, later the 12 x kTopkMaxK values on their way to rank order
+// (even: the list behind it is 8-byte aligned)
+__host__ __device__ inline int cp_topk_keys_words(int hw) { return (max(hw + hw / 16 + 1, 12 * kTopkMaxK) + 1) & ~1; }
 
 __global__ __launch_bounds__(kTopkThreads) void cp_topk_kernel(CpHeads h, CpCfg c, int* __restrict__ counts,
                                                                int* __restrict__ pool_counts, int cap, CpRows rows, int key_bits) {
   extern __shared__ __attribute__((aligned(16))) unsigned char topk_smem[];
   const int hw = c.hw;
-  uint32_t* ks = reinterpret_cast<uint32_t*>(topk_smem);                       // [hw]
-  unsigned long long* list = reinterpret_cast<unsigned long long*>(ks + ((max(hw + hw / 16 + 1, 12 * kTopkMaxK) + 1) & ~1));  // [kTopkMaxK]
-  int* hist = reinterpret_cast<int*>(list + kTopkMaxK);                        // [kTopkCopies][1024]
-  int* scr = hist + kTopkCopies * 1024;                                                      // [32]: scan scratch, [30], [31] broadcast
-  uint64_t* etab = reinterpret_cast<uint64_t*>(scr + 32);                                    // [32]: expf's table
+  uint32_t* ks = reinterpret_cast<uint32_t*>(topk_smem);                                           // [hw]: kidx
+  unsigned long long* list = reinterpret_cast<unsigned long long*>(ks + cp_topk_keys_words(hw));  // [kTopkMaxK]
+  int* hist = reinterpret_cast<int*>(list + kTopkMaxK);                                            // [kTopkHistWords]
+  int* scr = hist + kTopkHistWords;                                                                // [kTopkScratch]
+  uint64_t* etab = reinterpret_cast<uint64_t*>(scr + kTopkScratch);                                // [32]: expf's table
   unsigned char* cls = reinterpret_cast<unsigned char*>(etab + 32);                          // [hw]: best class of a cell
   const int set = blockIdx.x, sets = gridDim.x;
   if (threadIdx.x < 32) etab[threadIdx.x] = lm::exp2f_tab((int)threadIdx.x);
@@ -295,9 +292,8 @@ __global__ __launch_bounds__(kTopkThreads) void cp_topk_kernel(CpHeads h, CpCfg 
       }
     }
   }
-  for (int i = threadIdx.x; i < kTopkMaxK; i += kTopkThreads) list[i] = ~0ull;
   int count;
-  block_exclusive_scan<kTopkThreads>(selected, scr, count);  // (its barriers also publish ks / list)
+  block_exclusive_scan<kTopkThreads>(selected, scr, count);  // (its barriers also publish ks)
   if (threadIdx.x == 0) {
     counts[set] = count;
     // the two counters the suppression-matrix kernels append through (nms_kernels.hpp NmsPool): no set-up memset
@@ -306,89 +302,16 @@ __global__ __launch_bounds__(kTopkThreads) void cp_topk_kernel(CpHeads h, CpCfg 
   }
   const int K = min(count, cap);
   if (K <= 0) return;
-  // ---- cut-off key kc and the number r of cells with key == kc that are taken (0: take every key < kc) -----
-  // Radix select over the key_bits bits a masked-in key can have (scores above the threshold: 25 bits at 0.1 -- the
-  // bits above are zero, and a digit taken from them put all cells into 27 bins), ten bits at a time from the top;
-  // it stops as soon as the bin holding the cut-off is needed whole, which after two digits (16 k cells over a million
-  // bins) it nearly always is.
-  uint32_t kc = kKeyOut;
-  int r = 0;
-  if (count > K) {
-    uint32_t prefix = 0;  // decided high bits
-    int need = K;         // rank of the cut-off inside the still-undecided set (1-based)
-    int hi = key_bits;    // bits [0, hi) are undecided
-    while (hi > 0) {
-      const int w = min(hi, 10), shift = hi - w;
-      for (int i = threadIdx.x; i < kTopkCopies * 1024; i += kTopkThreads) hist[i] = 0;
-      __syncthreads();
-      for (int i = threadIdx.x; i < hw; i += kTopkThreads) {
-        const uint32_t k = ks[kidx(i)];
-        if ((k >> hi) == prefix)
-          atomicAdd(&hist[(threadIdx.x & (kTopkCopies - 1)) * 1024 + ((k >> shift) & ((1u << w) - 1u))], 1);
-      }
-      __syncthreads();
-      // thread t owns bins kBpt t .. kBpt t + kBpt - 1: exclusive prefix over bins, find the bin holding rank `need`
-      constexpr int kBpt = 1024 / kTopkThreads;
-      const int b0 = threadIdx.x * kBpt;
-      int hh[kBpt], hsum = 0;
-#pragma unroll
-      for (int j = 0; j < kBpt; ++j) {
-        hh[j] = 0;
-#pragma unroll
-        for (int c = 0; c < kTopkCopies; ++c) hh[j] += hist[c * 1024 + b0 + j];
-        hsum += hh[j];
-      }
-      int total;
-      const int base = block_exclusive_scan<kTopkThreads>(hsum, scr, total);
-      int cum = base;
-#pragma unroll
-      for (int j = 0; j < kBpt; ++j) {
-        if (need > cum && need <= cum + hh[j]) {  // exactly one (thread, j) satisfies this
-          scr[29] = hh[j];
-          scr[30] = b0 + j;
-          scr[31] = need - cum;
-        }
-        cum += hh[j];
-      }
-      __syncthreads();
-      const int in_bin = scr[29];
-      prefix = (prefix << w) | (uint32_t)scr[30];
-      need = scr[31];
-      hi = shift;
-      __syncthreads();
-      if (need == in_bin) {  // the whole bin is taken: every key below the next prefix, none at it
-        prefix = (prefix + 1u) << hi;
-        need = 0;
-        break;
-      }
-    }
-    kc = prefix;
-    r = need;
-  }
-  // ---- compaction in cell order: thread t owns the contiguous cells [t*ept, (t+1)*ept) ------------------------
-  const int ept = (hw + kTopkThreads - 1) / kTopkThreads;
-  const int c0 = threadIdx.x * ept, c1 = min(c0 + ept, hw);
-  int nless = 0, neq = 0;
-  for (int i = c0; i < c1; ++i) {
-    const uint32_t k = ks[kidx(i)];
-    nless += k < kc ? 1 : 0;
-    neq += k == kc ? 1 : 0;
-  }
-  int tot_less, tot_eq;
-  int pos_less = block_exclusive_scan<kTopkThreads>(nless, scr, tot_less);
-  int pos_eq = block_exclusive_scan<kTopkThreads>(neq, scr, tot_eq);
-  // entry = key : cell : position in this (cell-ordered) list -- the order of (key, cell) with the way back to the position
-  for (int i = c0; i < c1; ++i) {
-    const uint32_t k = ks[kidx(i)];
-    if (k < kc) {
-      list[pos_less] = ((unsigned long long)k << 32) | (uint32_t)(i << 10) | (uint32_t)pos_less;
-      ++pos_less;
-    } else if (k == kc) {
-      if (pos_eq < r) list[tot_less + pos_eq] = ((unsigned long long)k << 32) | (uint32_t)(i << 10) | (uint32_t)(tot_less + pos_eq);
-      ++pos_eq;
-    }
-  }
-  __syncthreads();
+  // ---- selection (block_topk.hpp); at a positive threshold kKeyOut lies above key_bits and is not counted ----------
+  // entry = key : cell : position in this list -- the order of (key, cell) with the way back to the position
+  const TopkCut cut = count > K ? block_topk_cut(K, key_bits, hist, scr,
+                                                 [&](auto f) {
+                                                   for (int i = threadIdx.x; i < hw; i += kTopkThreads) f(ks[kidx(i)]);
+                                                 })
+                                : TopkCut{kKeyOut, 0};
+  block_topk_compact_chunks(
+      cut, hw, [&](int i) { return ks[kidx(i)]; }, [](int i, int pos) { return (uint32_t)(i << 10) | (uint32_t)pos; },
+      list, scr);
   // ---- the head values of the selected cells: fetched NOW, by thread p for the p-th cell in cell order ---------
   // Ten reads of four bytes from ten planes per cell are the slowest thing the decode does (17 of its 22 us when it
   // came after the sort).  Issued here they are in flight during the sort, whose barriers (px_lds_barrier) wait for
@@ -405,34 +328,7 @@ __global__ __launch_bounds__(kTopkThreads) void cp_topk_kernel(CpHeads h, CpCfg 
     my = cp_gather_cell(h, c, t_of, frame_of, my_cell);
   }
   const int my_cls = cls[my_cell];
-  // ---- bitonic sort of the entries, padded with ~0: one compare-exchange per thread and step ---------------------
-  // Thread t of wave w works on entries [128 w, 128 w + 128) at every stride up to 64 -- entries no other wave touches
-  // at such a step -- so those steps follow each other in the wave's own LDS order; a barrier is only needed around the
-  // steps with a stride of 128 and more: 10 of them at 1024 entries instead of one after each of the 55 steps.
-  {
-    int n2 = 64;
-    while (n2 < K) n2 <<= 1;  // uniform
-    const int t = threadIdx.x;
-    for (int size = 2; size <= n2; size <<= 1) {
-      for (int stride = size >> 1; stride > 0; stride >>= 1) {
-        if (t < (n2 >> 1)) {
-          const int lo = 2 * t - (t & (stride - 1));
-          const int hi = lo + stride;
-          const bool up = (lo & size) == 0;
-          const unsigned long long a = list[lo], b = list[hi];
-          if ((a > b) == up) {
-            list[lo] = b;
-            list[hi] = a;
-          }
-        }
-        if (stride >= 2 * kWave || (stride == 1 && size >= 2 * kWave))
-          px_lds_barrier();
-        else
-          asm volatile("" ::: "memory");
-      }
-    }
-    px_lds_barrier();
-  }
+  block_topk_sort(list, K);  // its barriers wait for LDS only: the gathers above stay in flight
   // ---- position -> rank, then the fetched values travel to their rank through LDS (the keys' 64 KB are free) ------
   unsigned short* rank_of = reinterpret_cast<unsigned short*>(hist);  // [kTopkMaxK]
   float* vals = reinterpret_cast<float*>(ks);                          // [12][kTopkMaxK]
@@ -468,11 +364,10 @@ __global__ __launch_bounds__(kTopkThreads) void cp_topk_kernel(CpHeads h, CpCfg 
   }
 }
 
-// LDS of cp_topk_kernel: keys (later the 12 x 1024 values on their way to rank order), list, histograms, scan scratch,
-// expf's table, classes
-static inline size_t cp_topk_keys_words(int hw) { return std::max((size_t)hw + (size_t)hw / 16 + 1, (size_t)12 * kTopkMaxK); }
+// LDS of cp_topk_kernel: keys / values, list, histograms, scan scratch, expf's table, classes
 static inline size_t cp_topk_lds(int hw) {
-  return cp_topk_keys_words(hw) * 4 + 8 + (size_t)kTopkMaxK * 8 + (size_t)kTopkCopies * 1024 * 4 + 32 * 4 + 32 * 8 + (size_t)hw;
+  return (size_t)cp_topk_keys_words(hw) * 4 + (size_t)kTopkMaxK * 8 + (size_t)kTopkHistWords * 4 + kTopkScratch * 4 +
+         32 * 8 + (size_t)hw;
 }
 
 // The full-sort selection's last pass: the nms_pre_max_size best cells of every set, in sorted order.
@@ -680,13 +575,8 @@ static int cp_postprocess_impl(
     const size_t lds = cp_topk_lds(hw);
     e = pd3_max_dynamic_lds(reinterpret_cast<const void*>(cp_topk_kernel), (int)cp_topk_lds(kTopkMaxHw));
     if (e != hipSuccess) return (int)e;
-    // bits a masked-in key can have: key = bits(1.0f) - bits(score) with score in (threshold, 1]
-    uint32_t thr_bits;
-    memcpy(&thr_bits, &score_threshold, 4);
-    const uint32_t top = (score_threshold > 0.f && thr_bits < kKeyOne) ? kKeyOne - thr_bits : kKeyOne;
-    int key_bits = 1;
-    while (key_bits < 30 && (top >> key_bits) != 0) ++key_bits;
-    cp_topk_kernel<<<sets, kTopkThreads, lds, s>>>(h, c, w.counts, w.pool.counts, cap, rows, key_bits);
+    cp_topk_kernel<<<sets, kTopkThreads, lds, s>>>(h, c, w.counts, w.pool.counts, cap, rows,
+                                                   topk_key_bits(score_threshold));
   } else {
     e = hipMemsetAsync(w.counts, 0, (size_t)((char*)(w.pool.counts + (size_t)sets * 2 * kNmsCtrStride) - (char*)w.counts), s);
     if (e != hipSuccess) return (int)e;

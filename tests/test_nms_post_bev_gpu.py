@@ -212,7 +212,7 @@ def test_postprocess_zero_pre_nms_cap(oracle):
     assert b.shape[0] == 0 and s.shape[0] == 0 and l.shape[0] == 0
 
 
-@pytest.mark.parametrize("pre", [37, 100, 1000])
+@pytest.mark.parametrize("pre", [1, 37, 64, 65, 100, 128, 1000, 1024])
 def test_postprocess_topk_select_equals_full_sort(oracle, pre):
     """The LDS top-K selection (cut-off key + ties in cell order) gives exactly the full stable sort's result,
     also when many cells share one score: quantised heat maps put hundreds of ties at the cut-off."""

@@ -136,13 +136,14 @@ def test_ssd_postprocess_vs_reference_python(oracle, sg, tag):
         assert int(nn[1]) == 0 and float(ss[1, 0]) == -1.0 and int(ll[1, 0]) == -1 and float(bb[1, 0].abs().sum()) == 0
 
 
-@pytest.mark.parametrize("batch,seed,thr,pre", [(3, 1, 0.05, 1000), (2, 2, 0.6, 1000), (2, 3, 0.02, 1500),
-                                                 (2, 5, 0.6, 4096)])
+@pytest.mark.parametrize("batch,seed,thr,pre", [(3, 1, 0.05, 1000), (2, 2, 0.6, 1000), (2, 4, 0.05, 1024),
+                                                 (2, 3, 0.02, 1500), (2, 5, 0.6, 4096)])
 def test_ssd_postprocess_kitti_size_vs_oracle(oracle, batch, seed, thr, pre):
     """Full KITTI head map (248 x 216 x 2 = 107 136 anchors per frame) against the oracle restatement on the same
     inputs: identical rows, labels and order; boxes / scores within an ulp of exp.  Top-K selection kernel and full
-    sort; a pre-NMS cap beyond the selection kernel's 1024 (which takes the sort by itself); a cap of 4096 with a
-    few hundred candidates per frame (the NMS sweep's in-LDS path under a capacity it was not sized for once)."""
+    sort, also at the selection kernel's largest cap (1024: a full bitonic list); a pre-NMS cap beyond that 1024
+    (which takes the sort by itself); a cap of 4096 with a few hundred candidates per frame (the NMS sweep's in-LDS
+    path under a capacity it was not sized for once)."""
     from paddle3d_amd.pointpillars import KITTI_CAR_ANCHORS, AnchorGenerator, SSDHead
 
     pcr, vs = list(synth.KITTI_RANGE), list(synth.KITTI_PILLAR)
