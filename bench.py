@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- scenes/s of the CenterPoint-Pillars nuScenes hot path on N MI355X (one process per GPU).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--workload W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--workload W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -17,14 +17,23 @@ Rank 0 prints ONE JSON line.  Weak scaling: every rank processes its own batch, 
 
 The line also carries
   roofline      hard_voxelize's launch sequence (the op the north star sets the >=50 % HBM target on):
-                algorithmic bytes per launch / its HIP-event duration inside the timed region;
-  rooflines     the same for the other ops: scatter / postprocess on HBM; PFN and the dense graph on the fp32
-                MFMA peak, both as EXECUTED flops (what the matrix cores do) and as direct-form flops;
+                algorithmic bytes per launch / its HIP-event duration inside W + K steps of the pair form of the
+                graph, a block of its own (--full; a plain run leaves achieved / frac null);
+  rooflines     the same for the other ops, from the timed steps' own HIP events: scatter / postprocess on HBM;
+                PFN and the dense graph on the fp32 MFMA peak, both as EXECUTED flops (what the matrix cores do)
+                and as direct-form flops;
+and with --full only
   extras        h2d_inclusive scenes/s (the batch copied from pinned host memory inside every step), batch-1
                 latency, the copy / fill ceilings measured on this device;
   cpu_baseline  the oracle pipeline (reference CPU voxelizer compiled from /root/reference when present,
                 otherwise the port; torch-CPU dense graph) on a bounded sample, rank 0 at N=1 only: all host
                 threads, plus 1 thread and P processes x 1 thread.
+
+A plain run does only what the headline needs: set-up, W warm-up steps, the K timed steps, --dump-outputs and the
+line.  --full adds everything else: the repeated blocks (--repeats), the runs of their own (hard_voxelize's pair-form
+block, the other workloads, the H2D, batch-1, two-stream and strong-scaling passes), the comparisons (AMP and bf16x3
+against fp32, the mAP proxy) and the CPU baselines.  --repeats and --strong-frames, given explicitly, run their blocks
+in a plain run too.
 """
 from __future__ import annotations
 
@@ -80,18 +89,22 @@ def main(argv=None):
     ap.add_argument("--graph", action="store_true", help="replay the step as five captured HIP graphs (one per op) "
                     "instead of launching every kernel from the host (centerpoint_pillars; same kernels and buffers)")
     ap.add_argument("--repeats", type=int, default=None, help="time the same K steps this many more times after the "
-                    "contract block and report min / median / max (default 4 at N=1, 0 otherwise)")
+                    "contract block and report min / median / max (default 4 with --full at N=1, 0 otherwise)")
     ap.add_argument("--gather", choices=["overlap", "sync"], default="overlap", help="result hand-off: the all-gather "
                     "of batch k overlapped with batch k + 1 (default) or inside the step")
-    ap.add_argument("--strong-frames", type=int, default=128, help="frames of the fixed set of the strong-scaling extra "
-                    "(sharded over the ranks by dist.shard_frames; 0 = off)")
+    ap.add_argument("--strong-frames", type=int, default=None, help="frames of the fixed set of the strong-scaling extra "
+                    "(sharded over the ranks by dist.shard_frames; default 128 with --full unless --no-extras, 0 "
+                    "otherwise; 0 = off)")
     ap.add_argument("--no-affinity", action="store_true", help="do not pin the ranks of an N > 1 run to the cores next "
                     "to their GPUs")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="measure and check everything beside the headline too "
+                    "(extras, other workloads, comparisons, CPU baselines; see the module docstring); a plain run "
+                    "times only the headline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines and the mAP proxy")
     ap.add_argument("--map-frames", type=int, default=16, help="frames of the mAP proxy in extras (device detections "
                     "scored against the oracle pipeline's; ~1 s of CPU per frame; 0 = off)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the h2d-inclusive / batch-1 / ceiling measurements "
-                    "and the other workloads (profiling runs: only warm-up + timed steps are launched)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the h2d-inclusive / batch-1 / ceiling "
+                    "measurements and the other workloads")
     ap.add_argument("--stub-ops", action="store_true", help="test hook: no device ops, launch / collective path only "
                     "(CPU, gloo); the line is marked stub")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last "
@@ -103,7 +116,11 @@ def main(argv=None):
     if args.batch is None:
         args.batch = WORKLOADS[args.workload][1]
     if args.repeats is None:
-        args.repeats = 4 if args.gpus == 1 else 0
+        args.repeats = 4 if args.full and args.gpus == 1 else 0
+    if not args.full:  # a plain run: nothing beside the headline
+        args.no_extras = args.no_cpu_baseline = True
+    if args.strong_frames is None:
+        args.strong_frames = 0 if args.no_extras else 128
 
     # `python bench.py --gpus N` with no launcher around it: become the launcher
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:

@@ -102,7 +102,8 @@ def bench_camera_pool(args, rank, world, dev):
     80-84; cam_stream_lss.py:279-373): 6 views x 41 depth bins x 112 x 200 feature pixels, C = 64, onto 200 x 200 x 16
     cells of 0.5 m.  A step = frustum geometry -> index build (quantise, filter, sort, run-length) -> pooling, per
     batch of `--batch` scenes; the headline form pools depth [B*6, 41, 112, 200] and feat [B*6, 112, 200, 64] directly
-    (`lss_voxel_pooling_fused`), the second loop runs the reference's form on the lifted 1.41 GB / scene tensor."""
+    (`lss_voxel_pooling_fused`); with --full two loops in front of it time the reference's form on the lifted
+    1.41 GB / scene tensor and the pooling launch alone (`forms`)."""
     from paddle3d_amd import synth
     from paddle3d_amd.bevfusion import LiftSplatShoot
     from paddle3d_amd.ops import bev_pool_v2 as bp
@@ -148,21 +149,37 @@ def bench_camera_pool(args, rank, world, dev):
         mark(3)
         return out
 
+    forms = None
     with torch.no_grad():
-        import copy as _copy
+        if args.full:
+            import copy as _copy
 
-        a2 = _copy.copy(args)
-        a2.repeats, a2.dump_outputs = 0, None
-        dt_l, ms_l, out_l, _ = _timed_loop(run_lifted, a2, world, dev, ["start", "geometry", "lift", "index_build_and_pool"])
-        del out_l
-        torch.cuda.empty_cache()
-        # the pooling kernel alone, fixed calibration (index sets built once: what BEVDet calls `accelerate`)
-        geom0 = lss.get_geometry(rots, trans)
-        prep0 = bp.lss_pooling_prepare(geom0, lss.dx, lss.bx, lss.nx)
-        dt_a, ms_a, _o, _ = _timed_loop(
-            lambda ev: (ev[0].record() if ev is not None else None,
-                        bp.lss_voxel_pooling_fused(geom0, depth, feat, lss.dx, lss.bx, lss.nx, prepared=prep0),
-                        ev[1].record() if ev is not None else None)[1], a2, world, dev, ["start", "pool"])
+            a2 = _copy.copy(args)
+            a2.repeats, a2.dump_outputs = 0, None
+            dt_l, ms_l, out_l, _ = _timed_loop(run_lifted, a2, world, dev,
+                                               ["start", "geometry", "lift", "index_build_and_pool"])
+            del out_l
+            torch.cuda.empty_cache()
+            # the pooling kernel alone, fixed calibration (index sets built once: what BEVDet calls `accelerate`)
+            geom0 = lss.get_geometry(rots, trans)
+            prep0 = bp.lss_pooling_prepare(geom0, lss.dx, lss.bx, lss.nx)
+            dt_a, ms_a, _o, _ = _timed_loop(
+                lambda ev: (ev[0].record() if ev is not None else None,
+                            bp.lss_voxel_pooling_fused(geom0, depth, feat, lss.dx, lss.bx, lss.nx, prepared=prep0),
+                            ev[1].record() if ev is not None else None)[1], a2, world, dev, ["start", "pool"])
+            lifted_bytes = 4 * B * 6 * lss.D * lss.fH * lss.fW * C
+            forms = {
+                "fused_fixed_calibration": dict(value=world * B * a2.steps / dt_a, unit="frames/s",
+                                                ms_per_step=dt_a / a2.steps * 1e3, per_op_ms=ms_a,
+                                                note="index sets built once (fixed rig), the step is the pooling "
+                                                     "launch alone"),
+                "lifted_reference_form": dict(value=world * B * a2.steps / dt_l, unit="frames/s",
+                                              ms_per_step=dt_l / a2.steps * 1e3, per_op_ms=ms_l,
+                                              lifted_tensor_bytes=lifted_bytes,
+                                              note="CamEncode's lift x = depth (x) feat written to HBM (1.41 GB / scene), "
+                                                   "then voxel_pooling(geom, x) through the same kernels with unit "
+                                                   "weights: the reference's data flow; same result bit for bit "
+                                                   "(tests/test_lss_c5_gpu.py)")}
         dt, per_op_ms, out, info = _timed_loop(run_fused, args, world, dev, names)
     if rank != 0:
         return None
@@ -171,7 +188,6 @@ def bench_camera_pool(args, rank, world, dev):
     out_elems = int(out.numel())
     alg = 4 * (n_pts * (1 + C) + 3 * n_pts + 2 * n_int) + 4 * out_elems   # SURVEY 8(d), gathered operands once per use
     compulsory = 4 * (int(depth.numel()) + int(feat.numel()) + 3 * n_pts + 2 * n_int + out_elems)
-    lifted_bytes = 4 * B * 6 * lss.D * lss.fH * lss.fW * C
     # HBM-side traffic of the pooling launch from the committed PMC passes (tools/gpu_kernel_traffic.sh: the run launches
     # the kernel in its lifted form first, then on split operands: the later dispatches are the fused form), + the zero
     # fill of the output the entry point issues in front of it; one scene per launch
@@ -206,17 +222,9 @@ def bench_camera_pool(args, rank, world, dev):
                                       "once per use); compulsory = each tensor once (depth + feat + index sets + output): "
                                       "the 34 MB / scene of feat rows are re-read from cache 13 x on average"),
         "per_op_ms": per_op_ms, "kept_points": n_pts, "intervals": n_int,
-        "forms": {
-            "fused_fixed_calibration": dict(value=world * B * a2.steps / dt_a, unit="frames/s", ms_per_step=dt_a / a2.steps * 1e3,
-                                            per_op_ms=ms_a, note="index sets built once (fixed rig), the step is the "
-                                                                 "pooling launch alone"),
-            "lifted_reference_form": dict(value=world * B * a2.steps / dt_l, unit="frames/s", ms_per_step=dt_l / a2.steps * 1e3,
-                                          per_op_ms=ms_l, lifted_tensor_bytes=lifted_bytes,
-                                          note="CamEncode's lift x = depth (x) feat written to HBM (1.41 GB / scene), then "
-                                               "voxel_pooling(geom, x) through the same kernels with unit weights: the "
-                                               "reference's data flow; same result bit for bit "
-                                               "(tests/test_lss_c5_gpu.py)")},
     }
+    if forms is not None:
+        line["forms"] = forms
     if world == 1 and not args.no_cpu_baseline:
         try:
             line["cpu_baseline"] = camera_pool_cpu_baseline()

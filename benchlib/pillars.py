@@ -358,9 +358,9 @@ def bench_pillars(args, rank, world, dev):
     # the fused front the contract block's step no longer contains it, so it is timed in a block of its own, in the
     # contract's own shape (the same _timed_loop: barrier, W warm-up steps, K timed steps of the PAIR form of the graph
     # with the result hand-off, HIP events around the operator, the points evicted by the rest of the step) in front of
-    # the contract block.  `value` / `ms_per_step` are the contract block's (fused front).
+    # the contract block, with --full only.  `value` / `ms_per_step` are the contract block's (fused front).
     pair_ms = None
-    if fused_front:
+    if fused_front and args.full:
         import copy as _copy
 
         a2 = _copy.copy(args)
@@ -483,9 +483,9 @@ def bench_pillars(args, rank, world, dev):
                 print(f"bench: HIP-graph capture failed ({type(e).__name__}: {e}); running the eager step", file=sys.stderr)
                 step, launch = (lambda ev: run(pts, ev)), "eager (graph capture failed)"
     dt, per_op_ms, out, info = _timed_loop(step, args, world, dev, names, finish=finish)
-    op_ms = per_op_ms if pair_ms is None else pair_ms
+    op_ms = pair_ms if fused_front else per_op_ms  # None: a plain run has no pair-form block
     multi = {}
-    if args.strong_frames > 0 and not args.no_extras:
+    if args.strong_frames > 0:
         # every rank takes part (collectives inside); the line is rank 0's
         loop = dict(_LAST_LOOP)
         with torch.no_grad():
@@ -523,6 +523,17 @@ def bench_pillars(args, rank, world, dev):
                              executed_flops_per_unit=sum(by_pipe.values()), direct_form_flops_per_unit=direct,
                              direct_form_tflops=direct * B / (ms * 1e-3) / 1e12, note=note)
 
+    if op_ms is None:  # the operator's own block is a --full measurement
+        vox_roofline = dict(bound="hbm", achieved=None, peak=HBM_PEAK_GBPS, unit="GB/s", frac=None, traffic=None,
+                            ms_per_launch=None, units_per_launch=B, measured_in=None,
+                            note="the contract block's step runs pd3_hard_voxelize_index, not the operator; its own "
+                                 "block of the pair form runs with --full")
+    else:
+        vox_roofline = dict(hbm("hard_voxelize", "hard_voxelize", op_ms),
+                            measured_in=("W + K steps of the pair form of the graph (pd3_hard_voxelize + "
+                                         "pd3_pillar_feature_net), run in front of the contract block: the contract "
+                                         "block's step holds pd3_hard_voxelize_index instead, see front_half")
+                            if fused_front else "the contract block's steps")
     d_direct, d_exec = dense_flops()
     with torch.no_grad():
         vox_out = model.voxelizer(pts)
@@ -530,11 +541,7 @@ def bench_pillars(args, rank, world, dev):
         first_pairs = first_layer_pairs(vox_out[1]) / B
     p_direct, p_exec = pfn_flops(V, pfn_mfma)
     rooflines = dict(
-        hard_voxelize=dict(hbm("hard_voxelize", "hard_voxelize", op_ms),
-                           measured_in=("W + K steps of the pair form of the graph (pd3_hard_voxelize + pd3_pillar_feature_net), "
-                                        "run in front of the contract block: the contract block's step holds "
-                                        "pd3_hard_voxelize_index instead, see front_half") if fused_front
-                           else "the contract block's steps",
+        hard_voxelize=dict(vox_roofline,
                            input_state=("every step reads the same 16-frame batch (96 MB: it would fit the 256 MB Infinity "
                                         "Cache), but the 8 ms of convolutions between two voxelizer runs evict it -- the "
                                         "route kernel takes ~30 us inside the step against ~24 us when the operator is "
@@ -602,16 +609,17 @@ def bench_pillars(args, rank, world, dev):
             form=("fused: pd3_hard_voxelize_index (no padded [V, P, D] tensor) + pd3_pillar_feature_net_indexed"
                   if fused_front else "pair: pd3_hard_voxelize + pd3_pillar_feature_net"),
             ms_in_step=per_op_ms["hard_voxelize"] + per_op_ms["pillar_feature_net"],
-            pair_ms=dict(hard_voxelize=op_ms["hard_voxelize"], pillar_feature_net=op_ms["pillar_feature_net"]),
+            pair_ms=(dict(hard_voxelize=op_ms["hard_voxelize"], pillar_feature_net=op_ms["pillar_feature_net"])
+                     if op_ms is not None else None),
             note="per_op_ms.hard_voxelize / .pillar_feature_net are the intervals of the form the step runs; pair_ms are "
-                 "the two full operators inside K steps of the pair form"),
+                 "the two full operators inside K steps of the pair form (--full)"),
         # `roofline` is the kernel the north star puts the HBM target on; by time the step is dominated by
         # the dense graph (rooflines["dense_backbone_fpn_head"], MFMA bound)
         "dominant_by_time": "dense_backbone_fpn_head",
         "per_op_ms": per_op_ms,
         "detections_first_frame": int(out[1][0].item()),
     }
-    if amp:
+    if amp and args.full:
         # what the mixed-precision graph costs in accuracy on this batch: head maps against the fp32 graph's, and the
         # detections of the two graphs scored against each other on the mAP scale (the fp32 graph as the annotations)
         from paddle3d_amd import nuscenes_bridge as nb

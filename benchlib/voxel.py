@@ -144,7 +144,7 @@ def bench_voxel(args, rank, world, dev):
     }
     if overflow:
         line["error"] = "sparse plan: an index set outgrew its remembered capacity during the timed steps"
-    if not amp:
+    if not amp and args.full:
         from paddle3d_amd.ops import sparse_conv3d as _sp3
 
         with torch.no_grad():  # (untimed) the encoder's map by the fp32 matrix-core kernel in every layer, for comparison
@@ -161,7 +161,7 @@ def bench_voxel(args, rank, world, dev):
                  "matrix-core kernel (tests/test_sparse_conv_gpu.py::test_features_bf16x3_is_fp32_arithmetic)",
             encoder_map_max_abs_diff_vs_fp32_kernel=float((bev_x3 - bev_32).abs().max()),
             encoder_map_max_abs=float(bev_32.abs().max()))
-    if amp:
+    if amp and args.full:
         from paddle3d_amd import nuscenes_bridge as nb
 
         import copy

@@ -150,6 +150,23 @@ def test_single_rank_line_has_launch_fields():
     assert rb["blocks"] == 2 and rb["min"] <= rb["median"] <= rb["max"]
 
 
+def test_plain_run_times_only_the_headline():
+    """A plain run is set-up, warm-up, the K timed steps and the line; --full adds the repeated blocks and the extras
+    (here the strong-scaling and H2D passes) around the same timed loop; an extra asked for by its own option runs in
+    a plain run too."""
+    base = ["--gpus", "1", "--stub-ops", "--steps", "2", "--warmup", "1", "--batch", "2"]
+    lines = {}
+    for name, extra in (("plain", []), ("full", ["--full", "--strong-frames", "4"]), ("asked", ["--strong-frames", "4"])):
+        r = _run(base + extra)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines[name] = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+        assert lines[name]["steps"] == 2 and lines[name]["warmup"] == 1 and lines[name]["ms_per_step"] > 0
+    assert lines["plain"]["extras"] == {}
+    ex = lines["full"]["extras"]
+    assert ex["repeat_blocks"]["blocks"] == 4 and ex["strong_scaling"]["frames"] == 4 and ex["h2d_inclusive"]["value"] > 0
+    assert sorted(lines["asked"]["extras"]) == ["h2d_inclusive", "h2d_overlapped", "strong_scaling"]
+
+
 def test_refuses_more_gpus_than_visible():
     if torch.cuda.is_available() and torch.cuda.device_count() >= 2:
         return  # a 2+-GPU box may run it for real

@@ -4,7 +4,7 @@
 # stages, run in the order given; every output lands under gpurun_out/<tag>_* (copy what is to be judged to profiles/):
 #   tests[=<pytest -k expression>]   the GPU suite (or the selected tests), tail in <tag>_tests.log
 #   smoke                            __graft_entry__.smoke()
-#   bench[=<workload>]               the bench line (default workload, or --workload <w>) -> <tag>_bench[_<w>].json
+#   bench[=<workload>]               the --full bench line (default workload, or --workload <w>) -> <tag>_bench[_<w>].json
 #   prof[=<workload>]                rocprofv3 --kernel-trace --stats of 10 steps -> <tag>_step[_<w>]_kernels.txt
 #   traffic                          two --pmc passes (FETCH_SIZE / WRITE_SIZE) over the default step
 #   vox[=<paths>]                    hard_voxelize alone per path (tools/gpu_vox.sh, no pytest) -> <tag>_vox_paths.txt
@@ -24,7 +24,7 @@ for stage in "$@"; do
     smoke)
       timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 | tee gpurun_out/${tag}_smoke.log ;;
     bench)
-      sfx=""; wl=""; [ -n "$arg" ] && sfx=_$arg && wl="--workload $arg"
+      sfx=""; wl="--full"; [ -n "$arg" ] && sfx=_$arg && wl="--full --workload $arg"
       timeout 900 python bench.py $wl > gpurun_out/${tag}_bench${sfx}.json 2> gpurun_out/${tag}_bench${sfx}.err
       python - <<PY
 import json
