@@ -387,6 +387,37 @@ int pd3_bevdet4d_align(const float *const *feats, const int64_t *strides, int nu
                        void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * ms_deform_attn / its gradient -- replace PD_BUILD_OP(ms_deform_attn) and PD_BUILD_GRAD_OP(ms_deform_attn)
+ * (ms_deform_attn/ms_deform_attn.cc:85-101; kernels ms_deform_attn_cuda_kernel.h:37-84 bilinear sample, :86-151 its
+ * gradient, :220-274 the forward loop).  BEVFormer's TemporalSelfAttention, MSDeformableAttention3D and
+ * CustomMSDeformableAttention call it.
+ *
+ *   dtype: 0 float32, 1 float64 (every floating-point tensor of the call).
+ *   value [batch, spatial_size, num_heads, channels]; spatial_shapes [num_levels, 2] int64 (H, W) and
+ *     level_start_index [num_levels] int64, device memory, read by the kernels (no host round trip);
+ *     sampling_loc [batch, num_query, num_heads, num_levels, num_point, 2] (x, y) in [0, 1];
+ *     attn_weight [batch, num_query, num_heads, num_levels, num_point]; all contiguous.
+ *   out [batch, num_query, num_heads * channels].
+ *   The reference's im2col_step only slices the batch into launches; it does not change a result and is not a
+ *   parameter here (one launch).  Value rows outside [0, spatial_size) (spatial_shapes / level_start_index that
+ *   disagree with spatial_size) count as 0 and are never read; a level with H or W outside [1, 2^31 - 1] or
+ *   |level_start_index| > 2^62 contributes nothing.  Arithmetic order: csrc/ms_deform_attn.hip.
+ *   Backward: grad_out like out; writes grad_value (zeroed first, in stream order; float atomics: may differ in the
+ *   last bits from run to run), grad_sampling_loc and grad_attn_weight (like their inputs; bitwise reproducible).
+ *   PD3_EINVAL on dims < 1 (batch and num_query may be 0: nothing is launched, except the backward's zeroing of
+ *   grad_value when num_query is 0) or a dtype other than 0 / 1.
+ */
+int pd3_ms_deform_attn_forward(int dtype, const void *value, const int64_t *spatial_shapes,
+                               const int64_t *level_start_index, const void *sampling_loc, const void *attn_weight,
+                               int batch, int spatial_size, int num_heads, int channels, int num_levels,
+                               int num_query, int num_point, void *out, void *stream);
+int pd3_ms_deform_attn_backward(int dtype, const void *value, const int64_t *spatial_shapes,
+                                const int64_t *level_start_index, const void *sampling_loc, const void *attn_weight,
+                                const void *grad_out, int batch, int spatial_size, int num_heads, int channels,
+                                int num_levels, int num_query, int num_point, void *grad_value,
+                                void *grad_sampling_loc, void *grad_attn_weight, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * bev_pool_v2 / bev_pool_v2_bkwd -- replace PD_BUILD_OP(bev_pool_v2) (bev_pool_v2/bev_pool.cc:111-118,
  * kernel bev_pool_cuda.cu:18-44) and PD_BUILD_OP(bev_pool_v2_bkwd)
  * (bev_pool_v2_backward/bev_pool_bkwd.cc:75-80, kernel bev_pool_cuda_bkwd.cu:44-94).

@@ -79,6 +79,8 @@ _SIGNATURES = {
                                                       C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int,
                                                       C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                       C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pd3_ms_deform_attn_forward": (C.c_int, [C.c_int] + [C.c_void_p] * 5 + [C.c_int] * 7 + [C.c_void_p] * 2),
+    "pd3_ms_deform_attn_backward": (C.c_int, [C.c_int] + [C.c_void_p] * 6 + [C.c_int] * 7 + [C.c_void_p] * 4),
     "pd3_bev_pool_v2": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_int64, C.c_void_p,
                                                      C.c_void_p]),
     "pd3_bev_pool_v2_bkwd": (C.c_int, [C.c_void_p] * 8 + [C.c_int, C.c_int64, C.c_int, C.c_int64, C.c_int64,
