@@ -418,6 +418,72 @@ int pd3_ms_deform_attn_backward(int dtype, const void *value, const int64_t *spa
                                 void *grad_sampling_loc, void *grad_attn_weight, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * pointnet2 batch ops and points_in_boxes -- what IA-SSD calls (csrc/pointnet2.hip).  fp32 only, int32 indices,
+ * contiguous tensors; 64-bit offsets inside the kernels.  PD3_EINVAL on negative dims.
+ *
+ * farthest_point_sample -- replaces PD_BUILD_OP(farthest_point_sample) (pointnet2/sampling.cc:62, kernel
+ * sampling_gpu.cu:37-149).  xyz [batch, n, 3] -> idxs [batch, m].
+ *   Values: every minimum starts at 1e10 and is updated with fminf (a NaN distance never replaces it, a distance
+ *   above 1e10 is clamped to 1e10, so far points tie at 1e10); distance ((dx*dx + dy*dy) + dz*dz), dx = x2 - x1.
+ *   idxs[0] = 0.  m <= 0 writes nothing; m > n is legal and repeats indices under the same rule.  n = 0 with m > 0
+ *   is PD3_EINVAL; n > 2^24 is PD3_EUNSUPPORTED.
+ *   Ties: with bs = min(2^floor(log2 n), 1024) (the reference's opt_n_threads, sampling_gpu.cu:13-16), the winner
+ *   among equal maximum distances is the point with the smallest (bitreverse_{log2 bs}(k mod bs), k) -- what the
+ *   reference's per-thread strict > scan and its left-biased tree select; neither the smallest k nor the smallest
+ *   k mod bs.  (bs = 4: 1 vs 2 goes to 2; bs = 1024: 3 vs 1025 goes to 1025, 1 vs 512 to 512.)
+ *   tier: 0 auto, 1 register tier (n <= 16384, else PD3_EUNSUPPORTED: coordinates and minima in VGPRs, no spills),
+ *   2 general tier (n <= 2^24: minima of the first 65536 points of a frame in VGPRs, the rest in the workspace;
+ *   coordinates re-read from L2).  Auto picks the register tier for n <= 16384.  The workspace query returns the
+ *   bytes the call needs (0 for the register tier and for n <= 65536); PD3_EWORKSPACE if it is short.
+ */
+size_t pd3_farthest_point_sample_workspace(int batch, int n, int tier);
+int pd3_farthest_point_sample(const float *xyz, int batch, int n, int m, int tier, void *workspace,
+                              size_t workspace_bytes, int *idxs, void *stream);
+
+/* gather_operation / its gradient -- replace PD_BUILD_OP and PD_BUILD_GRAD_OP(gather_operation)
+ * (pointnet2/gather_points.cc:100-110, kernels gather_points_gpu.cu:25, 69).
+ *   points [batch, channels, n], idx [batch, npoints] -> out [batch, channels, npoints].
+ *   An index outside [0, n) reads as 0 (the reference reads arbitrary memory) and adds nothing to the gradient.
+ *   grad: grad_out [batch, channels, npoints] -> grad_points [batch, channels, n], zeroed first in stream order, then
+ *   float atomic adds: the last bits may vary from run to run, as the reference's do.
+ */
+int pd3_gather_points(const float *points, const int *idx, int batch, int channels, int n, int npoints, float *out,
+                      void *stream);
+int pd3_gather_points_grad(const float *grad_out, const int *idx, int batch, int channels, int n, int npoints,
+                           float *grad_points, void *stream);
+
+/* ball_query_batch -- replaces PD_BUILD_OP(ball_query_batch) (pointnet2_batch/ball_query_batch.cc:61, kernel
+ * ball_query_gpu_batch.cu:20-61).  new_xyz [batch, m, 3], xyz [batch, n, 3] -> idx [batch, m, nsample]: the first
+ * nsample points in index order with ((new_x - x)^2 + (new_y - y)^2) + (new_z - z)^2 < radius * radius (fp32), the
+ * unused slots filled with the first hit.  A row with no hit is 0 (the reference leaves paddle::empty memory there;
+ * 0 is what OpenPCDet's batch op returns and keeps grouping in bounds).
+ */
+int pd3_ball_query_batch(const float *new_xyz, const float *xyz, int batch, int n, int m, float radius, int nsample,
+                         int *idx, void *stream);
+
+/* grouping_operation_batch / its gradient -- replace PD_BUILD_OP and PD_BUILD_GRAD_OP(grouping_operation_batch)
+ * (pointnet2_batch/group_points_batch.cc:95-106, kernels group_points_gpu_batch.cu:25, 74).
+ *   points [batch, channels, n], idx [batch, npoints, nsample] -> out [batch, channels, npoints, nsample].
+ *   Indices outside [0, n) read as 0 and add nothing to the gradient.  grad: grad_out like out -> grad_points
+ *   [batch, channels, n], zeroed first in stream order, then float atomic adds (last bits may vary run to run).
+ */
+int pd3_group_points_batch(const float *points, const int *idx, int batch, int channels, int n, int npoints,
+                           int nsample, float *out, void *stream);
+int pd3_group_points_batch_grad(const float *grad_out, const int *idx, int batch, int channels, int n, int npoints,
+                                int nsample, float *grad_points, void *stream);
+
+/* points_in_boxes_gpu -- replaces PD_BUILD_OP(points_in_boxes_gpu) (roiaware_pool3d/box_utils.cc:65, kernel
+ * box_utils_gpu.cu:28-78).  pts [batch, npts, 3]; boxes rows (x, y, z, dx, dy, dz, heading), z at the centre, row k
+ * of frame b at boxes + b * box_batch_stride + k * box_row_stride floats (box_row_stride >= 7: the [:, :, 0:7] slice
+ * of an [B, M, 8] tensor is read in place) -> box_idx_of_points [batch, npts] int32: the first box in index order
+ * that holds the point, -1 if none.  cosf / sinf(-heading) carry glibc's bits; |z - cz| > dz / 2.0 and
+ * |local| < d / 2.0 + 1e-5f are evaluated in double, local_x / local_y in fp32 without FMA.  Boxes are staged in
+ * LDS 256 at a time (any nboxes).
+ */
+int pd3_points_in_boxes(const float *pts, const float *boxes, int batch, int npts, int nboxes, int64_t box_row_stride,
+                        int64_t box_batch_stride, int *box_idx_of_points, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * bev_pool_v2 / bev_pool_v2_bkwd -- replace PD_BUILD_OP(bev_pool_v2) (bev_pool_v2/bev_pool.cc:111-118,
  * kernel bev_pool_cuda.cu:18-44) and PD_BUILD_OP(bev_pool_v2_bkwd)
  * (bev_pool_v2_backward/bev_pool_bkwd.cc:75-80, kernel bev_pool_cuda_bkwd.cu:44-94).

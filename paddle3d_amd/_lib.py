@@ -81,6 +81,17 @@ _SIGNATURES = {
                                                       C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "pd3_ms_deform_attn_forward": (C.c_int, [C.c_int] + [C.c_void_p] * 5 + [C.c_int] * 7 + [C.c_void_p] * 2),
     "pd3_ms_deform_attn_backward": (C.c_int, [C.c_int] + [C.c_void_p] * 6 + [C.c_int] * 7 + [C.c_void_p] * 4),
+    "pd3_farthest_point_sample_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "pd3_farthest_point_sample": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                            C.c_void_p, C.c_void_p]),
+    "pd3_gather_points": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p]),
+    "pd3_gather_points_grad": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p]),
+    "pd3_ball_query_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int,
+                                       C.c_void_p, C.c_void_p]),
+    "pd3_group_points_batch": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p]),
+    "pd3_group_points_batch_grad": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p]),
+    "pd3_points_in_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64,
+                                      C.c_void_p, C.c_void_p]),
     "pd3_bev_pool_v2": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_int64, C.c_void_p,
                                                      C.c_void_p]),
     "pd3_bev_pool_v2_bkwd": (C.c_int, [C.c_void_p] * 8 + [C.c_int, C.c_int64, C.c_int, C.c_int64, C.c_int64,

@@ -1,0 +1,199 @@
+"""`paddle3d.ops.pointnet2_ops` mirror, batch ops (csrc/pointnet2.hip): what IA-SSD's SA layers call.
+
+farthest_point_sample(points, npoints)
+    points [B, N, 3] float32 -> idx [B, npoints] int32 (PD_BUILD_OP(farthest_point_sample), sampling.cc:62).
+    Ties among equal maximum distances follow the reference's thread layout (include/paddle3d_amd.h).
+gather_operation(points, idx)
+    points [B, C, N], idx [B, M] int32 -> [B, C, M] (gather_points.cc:100-110); differentiable in points.
+ball_query_batch(new_xyz, xyz, radius, nsample)
+    new_xyz [B, M, 3], xyz [B, N, 3] -> idx [B, M, nsample] int32 (ball_query_batch.cc:61); a row with no point
+    inside the ball is 0 (the reference leaves it undefined).
+grouping_operation_batch(points, idx)
+    points [B, C, N], idx [B, M, nsample] int32 -> [B, C, M, nsample] (group_points_batch.cc:95-106);
+    differentiable in points.
+
+float32 only, int32 indices, on the GPU.  Indices outside [0, N) read as 0 and add nothing to a gradient.  The
+gradients are summed with float atomics: their last bits may vary from run to run, as the reference's do.  Nothing
+here synchronises with the host.
+"""
+from __future__ import annotations
+
+import torch
+
+from ._common import check, lib, ptr, stream_ptr, workspace
+
+__all__ = ["farthest_point_sample", "gather_operation", "ball_query_batch", "grouping_operation_batch",
+           "gather_operation_grad", "grouping_operation_batch_grad", "GatherOperation", "GroupingOperationBatch"]
+
+
+def _gpu(t, op, what, dtype):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"Unsupported device type for {op} operator.")
+    if t.dtype != dtype:
+        raise RuntimeError(f"{op}: {what} must be {dtype}, got {t.dtype}")
+    return t
+
+
+def _same_device(op, *ts):
+    dev = ts[0].device
+    for t in ts[1:]:
+        if t.device != dev:
+            raise RuntimeError(f"{op}: tensors on {dev} and {t.device}")
+
+
+def _xyz(t, op, what):
+    _gpu(t, op, what, torch.float32)
+    if t.dim() != 3 or int(t.shape[2]) != 3:
+        raise RuntimeError(f"{op}: {what} must be [B, N, 3], got {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def farthest_point_sample(points, npoints, tier: int = 0):
+    """idx [B, npoints] int32.  tier 0 picks the kernel (register tier for N <= 16384); 1 / 2 force the register /
+    general tier (tests and measurements)."""
+    op = "farthest_point_sample"
+    xyz = _xyz(points, op, "points")
+    B, N = int(xyz.shape[0]), int(xyz.shape[1])
+    m = int(npoints)
+    idx = torch.empty((B, max(m, 0)), dtype=torch.int32, device=xyz.device)
+    if B == 0 or m <= 0:
+        return idx
+    if N == 0:
+        raise RuntimeError(f"{op}: no points to sample {m} from")
+    nbytes = int(lib().pd3_farthest_point_sample_workspace(B, N, int(tier)))
+    ws = workspace(nbytes, xyz.device) if nbytes else None
+    check(lib().pd3_farthest_point_sample(ptr(xyz), B, N, m, int(tier), ptr(ws), nbytes, ptr(idx),
+                                          stream_ptr(xyz.device)), op)
+    return idx
+
+
+def _features(points, op):
+    _gpu(points, op, "points", torch.float32)
+    if points.dim() != 3:
+        raise RuntimeError(f"{op}: points must be [B, C, N], got {tuple(points.shape)}")
+    return points.contiguous()
+
+
+def _gather_fwd(points, idx):
+    op = "gather_operation"
+    pts = _features(points, op)
+    _gpu(idx, op, "idx", torch.int32)
+    _same_device(op, pts, idx)
+    B, C, N = (int(s) for s in pts.shape)
+    if idx.dim() != 2 or int(idx.shape[0]) != B:
+        raise RuntimeError(f"{op}: idx must be [{B}, M], got {tuple(idx.shape)}")
+    M = int(idx.shape[1])
+    ix = idx.contiguous()
+    out = torch.empty((B, C, M), dtype=torch.float32, device=pts.device)
+    check(lib().pd3_gather_points(ptr(pts), ptr(ix), B, C, N, M, ptr(out), stream_ptr(pts.device)), op)
+    return out
+
+
+def gather_operation_grad(grad_out, idx, n):
+    """The grad op (gather_points.cc:108-110): grad_out [B, C, M], idx [B, M] -> grad_points [B, C, n]."""
+    op = "gather_operation_grad"
+    go = _features(grad_out, op)
+    _gpu(idx, op, "idx", torch.int32)
+    _same_device(op, go, idx)
+    B, C, M = (int(s) for s in go.shape)
+    if tuple(idx.shape) != (B, M):
+        raise RuntimeError(f"{op}: idx must be {(B, M)}, got {tuple(idx.shape)}")
+    gp = torch.empty((B, C, int(n)), dtype=torch.float32, device=go.device)
+    check(lib().pd3_gather_points_grad(ptr(go), ptr(idx.contiguous()), B, C, int(n), M, ptr(gp),
+                                       stream_ptr(go.device)), op)
+    return gp
+
+
+def _group_fwd(points, idx):
+    op = "grouping_operation_batch"
+    pts = _features(points, op)
+    _gpu(idx, op, "idx", torch.int32)
+    _same_device(op, pts, idx)
+    B, C, N = (int(s) for s in pts.shape)
+    if idx.dim() != 3 or int(idx.shape[0]) != B:
+        raise RuntimeError(f"{op}: idx must be [{B}, npoints, nsample], got {tuple(idx.shape)}")
+    P, S = int(idx.shape[1]), int(idx.shape[2])
+    out = torch.empty((B, C, P, S), dtype=torch.float32, device=pts.device)
+    check(lib().pd3_group_points_batch(ptr(pts), ptr(idx.contiguous()), B, C, N, P, S, ptr(out),
+                                       stream_ptr(pts.device)), op)
+    return out
+
+
+def grouping_operation_batch_grad(grad_out, idx, n):
+    """The grad op (group_points_batch.cc:103-106): grad_out [B, C, P, S], idx [B, P, S] -> grad_points [B, C, n]."""
+    op = "grouping_operation_batch_grad"
+    _gpu(grad_out, op, "grad_out", torch.float32)
+    if grad_out.dim() != 4:
+        raise RuntimeError(f"{op}: grad_out must be [B, C, npoints, nsample], got {tuple(grad_out.shape)}")
+    go = grad_out.contiguous()
+    _gpu(idx, op, "idx", torch.int32)
+    _same_device(op, go, idx)
+    B, C, P, S = (int(s) for s in go.shape)
+    if tuple(idx.shape) != (B, P, S):
+        raise RuntimeError(f"{op}: idx must be {(B, P, S)}, got {tuple(idx.shape)}")
+    gp = torch.empty((B, C, int(n)), dtype=torch.float32, device=go.device)
+    check(lib().pd3_group_points_batch_grad(ptr(go), ptr(idx.contiguous()), B, C, int(n), P, S, ptr(gp),
+                                            stream_ptr(go.device)), op)
+    return gp
+
+
+class GatherOperation(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, points, idx):
+        ctx.n = int(points.shape[2])
+        ctx.save_for_backward(idx)
+        ctx.mark_non_differentiable(idx)
+        return _gather_fwd(points, idx)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        (idx,) = ctx.saved_tensors
+        return gather_operation_grad(grad_out, idx, ctx.n), None
+
+
+class GroupingOperationBatch(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, points, idx):
+        ctx.n = int(points.shape[2])
+        ctx.save_for_backward(idx)
+        return _group_fwd(points, idx)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        (idx,) = ctx.saved_tensors
+        return grouping_operation_batch_grad(grad_out, idx, ctx.n), None
+
+
+def gather_operation(points, idx):
+    """[B, C, M] = points[b, c, idx[b, m]] (differentiable in points)."""
+    _features(points, "gather_operation")
+    _gpu(idx, "gather_operation", "idx", torch.int32)
+    return GatherOperation.apply(points, idx)
+
+
+def grouping_operation_batch(points, idx):
+    """[B, C, npoints, nsample] = points[b, c, idx[b, p, s]] (differentiable in points)."""
+    _features(points, "grouping_operation_batch")
+    _gpu(idx, "grouping_operation_batch", "idx", torch.int32)
+    return GroupingOperationBatch.apply(points, idx)
+
+
+def ball_query_batch(new_xyz, xyz, radius, nsample):
+    """idx [B, M, nsample] int32: the first nsample points of xyz, in index order, strictly inside the ball of
+    radius around each new_xyz row; unused slots repeat the first hit; rows without a hit are 0."""
+    op = "ball_query_batch"
+    q = _xyz(new_xyz, op, "new_xyz")
+    p = _xyz(xyz, op, "xyz")
+    _same_device(op, q, p)
+    B, M = int(q.shape[0]), int(q.shape[1])
+    if int(p.shape[0]) != B:
+        raise RuntimeError(f"{op}: new_xyz has batch {B}, xyz {int(p.shape[0])}")
+    N, S = int(p.shape[1]), int(nsample)
+    if S < 0:
+        raise RuntimeError(f"{op}: nsample must be >= 0, got {S}")
+    idx = torch.empty((B, M, S), dtype=torch.int32, device=q.device)
+    check(lib().pd3_ball_query_batch(ptr(q), ptr(p), B, N, M, float(radius), S, ptr(idx), stream_ptr(q.device)),
+          op)
+    return idx
