@@ -484,6 +484,58 @@ int pd3_points_in_boxes(const float *pts, const float *boxes, int batch, int npt
                         int64_t box_batch_stride, int *box_idx_of_points, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * pointnet2 stack ops -- what PV-RCNN's StackSAModuleMSG and Voxel R-CNN's NeighborVoxelSAModuleMSG call
+ * (csrc/pointnet2_stack.hip).  fp32 data, int32 indices and counts, contiguous tensors, 64-bit offsets inside the
+ * kernels.  The batch counts stay on the device: nothing here synchronises with the host.  PD3_EINVAL on negative
+ * dims, nsample < 1, or batch == 0 with rows to compute; m == 0 launches nothing.  batch > 256 is PD3_EUNSUPPORTED
+ * (every workgroup holds the counts' prefix in LDS, one per thread).
+ *   Frame of a row (ball query, grouping): the reference's scan (ball_query_gpu_stack.cu:37-42) -- the first
+ *   k < batch - 1 with row < cnt[0] + ... + cnt[k], else batch - 1.  A frame with count 0 is never picked; rows past
+ *   the total belong to frame batch - 1.  Sums are 64-bit (the reference's are int).
+ *   Query rows: the first nsample hits in the op's order, unused slots repeat the first hit, a row with no hit is
+ *   [-1, 0, 0, ...] (the reference fills paddle::full(0) and writes idx[0] = -1).  r2 = radius * radius in fp32.
+ *
+ * ball_query_stack -- replaces PD_BUILD_OP(ball_query_stack) (pointnet2_stack/ball_query_stack.cc:73, kernel
+ * ball_query_gpu_stack.cu:26-81).  new_xyz [m, 3], new_xyz_batch_cnt [batch], xyz [n, 3], xyz_batch_cnt [batch] ->
+ * idx [m, nsample], frame-local indices of the row's frame's points in index order with
+ * ((new_x - x)^2 + (new_y - y)^2) + (new_z - z)^2 < r2 (a NaN distance is no hit).  Departure: the frame's point range
+ * is computed with negative counts read as 0 and clamped into [0, n) (the reference reads outside xyz there);
+ * consistent counts are unaffected.
+ */
+int pd3_ball_query_stack(const float *new_xyz, const int *new_xyz_batch_cnt, const float *xyz,
+                         const int *xyz_batch_cnt, int batch, int m, int n, float radius, int nsample, int *idx,
+                         void *stream);
+
+/* voxel_query_wrapper -- replaces PD_BUILD_OP(voxel_query_wrapper) (pointnet2/voxel_query.cc:78, kernel
+ * voxel_query_gpu.cu:11-93).  new_xyz [m, 3], xyz [n, 3], new_coords [m, 4] as (b, z, y, x), point_indices
+ * [batch, z, y, x] -> idx [m, nsample]: rows of xyz, cells visited dz, then dy, then dx, each from -range to +range;
+ * cells outside the grid and point_indices < 0 are skipped.  Hit: !(((x - new_x)^2 + (y - new_y)^2) + (z - new_z)^2
+ * > r2) -- unlike the ball query, a point on the sphere and a NaN distance are hits.  The reference's cnt2 is unused
+ * and its curand_init has no effect, so the scan stops at nsample hits with the same result.  Departures: a batch
+ * index outside [0, batch) gives no hit and a point index >= n is skipped (both read out of bounds in the
+ * reference).  A negative range is an empty window, as the reference's loops are.  A window over 2^31 - 65 cells is
+ * PD3_EUNSUPPORTED.
+ */
+int pd3_voxel_query(const float *new_xyz, const float *xyz, const int *new_coords, const int *point_indices, int m,
+                    int n, int batch, int z, int y, int x, float radius, int nsample, int z_range, int y_range,
+                    int x_range, int *idx, void *stream);
+
+/* grouping_operation_stack / its gradient -- replace PD_BUILD_OP and PD_BUILD_GRAD_OP(grouping_operation_stack)
+ * (pointnet2_stack/group_points_stack.cc:117-130, kernels group_points_gpu_stack.cu:26-131).
+ *   features [n, channels], features_batch_cnt [batch], idx [m, nsample] (frame-local), idx_batch_cnt [batch] ->
+ *   out [m, channels, nsample], out[r, c, s] = features[start(frame(r)) + idx[r, s], c], start = the sum of the
+ *   earlier frames' features_batch_cnt.  A global row outside [0, n) reads as 0 (the reference reads arbitrary
+ *   memory) and adds nothing to the gradient.  grad: grad_out like out -> grad_features [n, channels], zeroed first in
+ *   stream order, then float atomic adds (the last bits may vary from run to run, as the reference's do).
+ */
+int pd3_group_points_stack(const float *features, const int *features_batch_cnt, const int *idx,
+                           const int *idx_batch_cnt, int batch, int n, int channels, int m, int nsample, float *out,
+                           void *stream);
+int pd3_group_points_stack_grad(const float *grad_out, const int *idx, const int *idx_batch_cnt,
+                                const int *features_batch_cnt, int batch, int n, int channels, int m, int nsample,
+                                float *grad_features, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * bev_pool_v2 / bev_pool_v2_bkwd -- replace PD_BUILD_OP(bev_pool_v2) (bev_pool_v2/bev_pool.cc:111-118,
  * kernel bev_pool_cuda.cu:18-44) and PD_BUILD_OP(bev_pool_v2_bkwd)
  * (bev_pool_v2_backward/bev_pool_bkwd.cc:75-80, kernel bev_pool_cuda_bkwd.cu:44-94).

@@ -43,8 +43,11 @@
 
 #include "common.hpp"
 #include "libm_exact.hpp"
+#include "pointnet2_common.hpp"
 
 namespace {
+
+using pd3::pn2::dist3;
 
 constexpr int kFpsThreads = 1024;
 constexpr int kFpsWaves = kFpsThreads / pd3::kWave;
@@ -77,11 +80,6 @@ __device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
     v = w > v ? w : v;
   }
   return v;
-}
-
-__device__ __forceinline__ float dist3(float x1, float y1, float z1, float x2, float y2, float z2) {
-  const float dx = x2 - x1, dy = y2 - y1, dz = z2 - z1;
-  return (dx * dx + dy * dy) + dz * dz;
 }
 
 // R: points (register tier) or minima (general tier) per lane held in VGPRs.
@@ -283,8 +281,7 @@ __global__ __launch_bounds__(kBqThreads) void ball_query_kernel(const float* __r
     const uint64_t mask = __ballot(hit);
     if (mask == 0) continue;
     if (cnt == 0) first = base + __ffsll((unsigned long long)mask) - 1;
-    const int pos = cnt + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
-                                                         __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+    const int pos = cnt + pd3::pn2::ballot_rank(mask);
     if (hit && pos < nsample) out[pos] = k;
     cnt += __popcll(mask);
   }
