@@ -536,6 +536,32 @@ int pd3_group_points_stack_grad(const float *grad_out, const int *idx, const int
                                 float *grad_features, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * assign_score_withk / its gradient -- replace PD_BUILD_OP and PD_BUILD_GRAD_OP(assign_score_withk)
+ * (assign_score_withk/assign_score_withk_cuda.cc:265-274, CPU kernels :32-158): PAConv's weight-bank assembly
+ * (csrc/assign_score_withk.hip).  fp32 data, int64 knn_idx, contiguous tensors, 64-bit offsets.
+ *   scores [batch, n, k, m], points [batch, n, m, o], centers [batch, n, m, o], knn_idx [batch, n, k] ->
+ *   output [batch, o, n]: for k, for m: acc = acc + points[b, kn, m, o] * s; acc = acc - centers[b, n, m, o] * s
+ *   (kn = knn_idx[b, n, k], s = scores[b, n, k, m], the reference CPU kernel's order, no fma).
+ *   Backward: grad_out like output -> grad_scores, grad_points, grad_centers like their inputs (each may be NULL to
+ *   skip it); orders in csrc/assign_score_withk.hip.  No float atomics: every output is bitwise reproducible.
+ *   Departures: kn outside [0, n) is range-tested as int64 and reads points as 0 (the forward still subtracts
+ *   c * s; grad_points gets nothing) where the reference truncates it to int and reads out of bounds; offsets are
+ *   64-bit; only fp32 (the reference's outputs are FLOAT32 whatever the input type); aggregate is SUM.
+ *   k == 0 or m == 0 gives an all-zero output.  PD3_EINVAL on negative dims; batch * n * k >= 2^31 is
+ *   PD3_EUNSUPPORTED, and so is a backward with batch > 65535.  Nothing synchronises with the host.
+ *   The backward's workspace (pd3_assign_score_withk_backward_workspace; needs no GPU) holds grad_out transposed
+ *   to [batch, n, o] and the inverse index of knn_idx (a stable radix sort per frame and segment starts).
+ */
+int pd3_assign_score_withk_forward(const float *scores, const float *points, const float *centers,
+                                   const int64_t *knn_idx, int batch, int n, int k, int m, int o, float *output,
+                                   void *stream);
+size_t pd3_assign_score_withk_backward_workspace(int batch, int n, int k, int o);
+int pd3_assign_score_withk_backward(const float *grad_out, const float *scores, const float *points,
+                                    const float *centers, const int64_t *knn_idx, int batch, int n, int k, int m,
+                                    int o, float *grad_scores, float *grad_points, float *grad_centers,
+                                    void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * bev_pool_v2 / bev_pool_v2_bkwd -- replace PD_BUILD_OP(bev_pool_v2) (bev_pool_v2/bev_pool.cc:111-118,
  * kernel bev_pool_cuda.cu:18-44) and PD_BUILD_OP(bev_pool_v2_bkwd)
  * (bev_pool_v2_backward/bev_pool_bkwd.cc:75-80, kernel bev_pool_cuda_bkwd.cu:44-94).

@@ -97,6 +97,10 @@ _SIGNATURES = {
     "pd3_voxel_query": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_float] + [C.c_int] * 4 + [C.c_void_p] * 2),
     "pd3_group_points_stack": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p] * 2),
     "pd3_group_points_stack_grad": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p] * 2),
+    "pd3_assign_score_withk_forward": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p] * 2),
+    "pd3_assign_score_withk_backward_workspace": (C.c_size_t, [C.c_int] * 4),
+    "pd3_assign_score_withk_backward": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_void_p] * 4 +
+                                        [C.c_size_t, C.c_void_p]),
     "pd3_bev_pool_v2": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_int64, C.c_void_p,
                                                      C.c_void_p]),
     "pd3_bev_pool_v2_bkwd": (C.c_int, [C.c_void_p] * 8 + [C.c_int, C.c_int64, C.c_int, C.c_int64, C.c_int64,
