@@ -94,6 +94,8 @@ int pd3_hard_voxelize_path(const float *points, const int32_t *num_points, int b
  *              point_list[b * max_points + start + 0 .. count - 1] (indices into frame b's rows of `points`,
  *              ascending = the reference's order inside a voxel); count == num_points_per_voxel
  *   point_list [pd3_hard_voxelize_index_list_entries(batch, max_points)] int32
+ *   Padding rows (v >= num_voxels[b]) of vox_span read (0, 0), those of coords / num_points_per_voxel / coors_batched
+ *   as in pd3_hard_voxelize; entries of point_list that no span names are scratch (unspecified).
  * A consumer reads a voxel's points from `points` itself (pd3_pillar_feature_net_indexed): the 78 %-zeros tensor is
  * neither written nor read.  Grids the wave forms do not serve (see pd3_hard_voxelize_path) return -3: run
  * pd3_hard_voxelize there.  Workspace: pd3_hard_voxelize_workspace. */
@@ -266,7 +268,8 @@ int pd3_libm_eval(int op, const float *x, const float *y, float *out, int64_t n,
  *   out_scores  [batch, same rows] fp32;  out_labels [batch, same rows] int64
  *   out_count   [batch] int32: number of valid leading rows per frame (tasks concatenated in order;
  *               a task with no candidate contributes the reference's fake row: zeros box, score -1,
- *               label 0).
+ *               label 0).  In all three forms below the rows behind it read zero in out_bboxes, out_scores
+ *               and out_labels: no output needs clearing by the caller.
  */
 size_t pd3_centerpoint_postprocess_workspace(int batch, int num_tasks, int feat_h, int feat_w,
                                              int nms_pre_max_size, int nms_post_max_size);
@@ -631,7 +634,11 @@ int pd3_voxel_pooling_prepare(const float *coor, int64_t num_points, int batch, 
  *   spatial_shape host int[3] (D, H, W);  kernel_size / stride / padding host int[3]
  *   subm != 0: output set = input set (same rows, same order); requires stride 1, padding = k/2
  *   subm == 0: output set = every position reached by an active input, rows sorted by (b, z, y, x)
- *   out_coords [out_cap, 4], nbr [out_cap, kd*kh*kw] int32 (input row or -1), n_out [1] int32 (device)
+ *   out_coords [out_cap, 4], nbr [out_cap, kd*kh*kw] int32 (input row or -1), n_out [1] int32 (device);
+ *   rows at or past *n_out of out_coords / nbr -- and of every feature matrix computed through them with that n_out --
+ *   are unspecified (a caller slices by the count).  subm != 0: *n_out = n_in and every row is written; the row of a
+ *   padding input holds out_coords = the input row, nbr = -1 throughout, and its features are the epilogue of an empty
+ *   sum.
  *   weight [kd, kh, kw, Cin, Cout] (Paddle layout); bias / scale+shift / residual may be NULL
  *   out = relu?( (sum_k W[k].in[nbr[.,k]] + bias) * scale + shift + residual ),  Cout <= 128
  */
@@ -739,7 +746,8 @@ int pd3_sparse_to_dense(const float *feats, const int32_t *coords, const int32_t
  *                  reader.py:150, e.g. the key frame repeated as padding at a scene start); time_lag host
  *                  float[num_sweeps] (NULL: zeros); remove_radius = sweep_remove_radius
  *   out            [<= total points, use_dim (+1 if use_time_lag)] fp32, rows in the reference's
- *                  concatenation order (given the sweep order); num_out [1] int32 (device)
+ *                  concatenation order (given the sweep order); num_out [1] int32 (device); allocate
+ *                  total points rows, rows at or past *num_out are unspecified
  */
 size_t pd3_merge_sweeps_workspace(int64_t num_points);
 int pd3_merge_sweeps(const float *points, const int64_t *sweep_offsets, int num_sweeps, int dim_in,
@@ -986,7 +994,9 @@ int pd3_conv3x3_s2_x3_bias_relu(const float *x, const void *w_packed, const floa
  *   center_limit_range  6 host floats or NULL (prediction_center_limit_range=None)
  * Outputs (device): out_boxes [batch, max(post,1), 7], out_scores [batch, max(post,1)], out_labels int64, out_count
  * [batch] int32.  A frame without detections (no anchor passes the area test, or none the score / range test) has
- * count 0 and the reference's `_box_empty` row (zeros, -1, -1) in row 0.  No host synchronisation.
+ * count 0 and the reference's `_box_empty` row (zeros, -1, -1) in row 0.  Rows behind out_count (behind row 0 of such a
+ * frame) are left to the caller: the Python shim clears the outputs first, and they then read zero.  No host
+ * synchronisation.
  * selection: how the top nms_pre_max_size anchors by score are found -- 0 = radix select + ordered compaction
  * (nms_pre_max_size <= 1024; larger caps take the sort), 1 = a full stable sort of every anchor's key (the
  * reference's argsort); identical results, the argument exists so that tests run both.

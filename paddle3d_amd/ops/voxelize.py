@@ -13,7 +13,7 @@ import torch
 from ._common import check, host_f32, lib, ptr, require_gpu, stream_ptr, workspace
 
 __all__ = ["dynamic_voxelize", "hard_voxelize", "hard_voxelize_batch", "hard_voxelize_index_batch",
-           "lds_atomic_order_ok"]
+           "lds_atomic_order_ok", "reset_lds_atomic_order_probe"]
 
 _LDS_ORDER = {}  # device index -> bool, probed once per process
 
@@ -60,6 +60,12 @@ def lds_atomic_order_ok(dev: torch.device) -> bool:
                       "hard_voxelize uses its sort form (slower, same results)", RuntimeWarning)
     _LDS_ORDER[key] = ok
     return ok
+
+
+def reset_lds_atomic_order_probe() -> None:
+    """Forget the cached verdicts: the next lds_atomic_order_ok(dev) probes the device again (tests run the probe
+    under guarded allocations this way)."""
+    _LDS_ORDER.clear()
 
 
 def hard_voxelize_batch(points: torch.Tensor, voxel_size, point_cloud_range, max_num_points_in_voxel: int,
