@@ -539,6 +539,71 @@ int pd3_group_points_stack_grad(const float *grad_out, const int *idx, const int
                                 float *grad_features, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Voxel R-CNN's RoI head (csrc/roi_head.hip): the fused voxel pool of NeighborVoxelSAModuleMSG, the RoI grid points,
+ * class-agnostic NMS for a whole batch and the box decode of the second stage.  Inference only.  fp32 data, int32
+ * indices, contiguous tensors, 64-bit offsets inside the kernels, no FMA, no float atomics; nothing here
+ * synchronises with the host.
+ *
+ * voxel_pool -- the inner part of NeighborVoxelSAModuleMSG.forward (pointnet2_stack/voxel_pool_modules.py:123-155) for
+ * one scale, from the voxel query to the pool, with no [m, *, nsample] tensor in global memory.  new_xyz [m, 3],
+ * new_coords [m, 4] as (b, z, y, x), xyz [n, 3], point_indices [batch, z, y, x], features_in [n, c1] (the output of
+ * mlps_in), w_pos [c1, 3], pos_scale / pos_shift [c1] (mlps_pos: the 1x1 conv weight and its BatchNorm in eval form,
+ * scale = gamma / sqrt(var + eps), shift = beta - mean * scale), pool 0 max / 1 avg ->
+ *   pooled [m, c1] = pool_s relu(features_in[idx[m, s]] + (pos_scale * ((w0 * dx + w1 * dy) + w2 * dz) + pos_shift))
+ * with idx exactly pd3_voxel_query's row for the same arguments (unused slots repeat the first hit, so a repeated
+ * slot takes part in an avg pool), d = xyz[idx] - new_xyz, and a row without a hit taking features = 0, d = 0 in all
+ * nsample slots.  relu(v) = v > 0 ? v : +0 (a NaN stays).  avg: with G = 64 / c1, the slots s = g, g + G, ... are
+ * summed in order for each g, the G sums by the tree (g0 + g1) + (g2 + g3), then divided by nsample.
+ * Departure from the reference: idx is used as rows of xyz directly (the reference subtracts and re-adds the frame's
+ * start; the same for consistent counts).  c1 not in {16, 32, 64} or nsample > 64: PD3_EUNSUPPORTED.
+ */
+int pd3_voxel_pool(const float *new_xyz, const float *xyz, const int *new_coords, const int *point_indices,
+                   const float *features_in, const float *w_pos, const float *pos_scale, const float *pos_shift, int m,
+                   int n, int batch, int z, int y, int x, int c1, float radius, int nsample, int z_range, int y_range,
+                   int x_range, int pool, float *pooled, void *stream);
+
+/* roi_grid_points -- RoIHeadBase.get_global_grid_points_of_roi + get_dense_grid_points (heads/roi_heads/
+ * roi_head_base.py:324-346) and the coordinates of VoxelRCNNHead.roi_grid_pool (voxelrcnn_head.py:165-183, 227-230).
+ * rois [num_rois, 7] (num_rois = frames * rois_per_frame) -> roi_grid_xyz [num_rois * G^3, 3] and, for each of
+ * num_strides <= 4 strides, coords [num_strides][num_rois * G^3, 4] as (b, x, y, z) =
+ * floor(floor((xyz - range_min) / voxel_size) / stride), b = roi / rois_per_frame; out of int32 range saturates, a
+ * NaN is 0.  Grid point i of a RoI is (ix, iy, iz) = (i / G^2, i / G % G, i % G) (nonzero()'s order);
+ * local = ((idx + 0.5) / G) * size - size / 2; rotation as the matmul's sums x' = (x * cos + y * (-sin)) + z * 0,
+ * y' = (x * sin + y * cos) + z * 0, z' = (x * 0 + y * 0) + z * 1 with glibc's cosf / sinf; then + centre.
+ * range_min, voxel_size [3] and strides are host arrays.
+ */
+int pd3_roi_grid_points(const float *rois, int64_t num_rois, int rois_per_frame, int grid_size, const float *range_min,
+                        const float *voxel_size, const int *strides, int num_strides, float *roi_grid_xyz, int *coords,
+                        void *stream);
+
+/* rcnn_decode_boxes -- RoIHeadBase.generate_predicted_boxes (roi_head_base.py:293-322) with
+ * ResidualCoder.decode_paddle (utils/box_coder.py:66-100, no sin / cos angle code, code size 7).  rois, box_preds
+ * [n, 7] -> out [n, 7]: diag = sqrtf(dxa * dxa + dya * dya); (xg, yg, zg) = (xt * diag + 0, yt * diag + 0,
+ * zt * dza + 0) rotated by the RoI's heading (the sums of roi_grid_points) + the RoI's centre; sizes expf(t) * a;
+ * heading rt + ra.  expf / sinf / cosf carry glibc's bits.
+ */
+int pd3_rcnn_decode_boxes(const float *rois, const float *box_preds, int64_t n, float *out, void *stream);
+
+/* class_agnostic_nms -- class_agnostic_nms (models/common/model_nms_utils.py:20-66) for a whole batch, as
+ * RoIHeadBase.proposal_layer (roi_head_base.py:70-131) and VoxelRCNN.post_processing (detection/voxel_rcnn/
+ * voxel_rcnn.py:145-220) call it.  box_preds [batch, num_boxes, 7], cls_preds [batch, num_boxes, num_classes],
+ * labels [batch, num_boxes] int64 or NULL.  Per frame: score = max over the classes (first maximum wins) of cls or,
+ * with apply_sigmoid, of 1 / (1 + expf(-cls)); rows with score >= score_thresh pass (a NaN score_thresh: all pass);
+ * stable descending order (ties by index, -0 == +0, a NaN score first); the first nms_pre_maxsize; rotated NMS on the
+ * 7 columns as they are (pd3_nms_bev's overlap, IoU > nms_thresh suppresses); the first nms_post_maxsize kept ->
+ * boxes [batch, post, 7], scores [batch, post], labels [batch, post] int64 (the 0-based argmax, or labels' entry),
+ * count [batch].  Rows behind count are zeros; under a score_thresh a frame that passes nothing gets the reference's
+ * box_empty row (zero box, score -1, label -1) in row 0 and count 0.  nms_pre_maxsize, nms_post_maxsize >= 1;
+ * nms_pre_maxsize > 65536 is PD3_EUNSUPPORTED.  The workspace query needs no GPU (0: shape not taken).
+ */
+size_t pd3_class_agnostic_nms_workspace(int batch, int64_t num_boxes, int nms_pre_maxsize);
+int pd3_class_agnostic_nms(const float *box_preds, const float *cls_preds, int batch, int64_t num_boxes,
+                           int num_classes, int apply_sigmoid, float score_thresh, const int64_t *labels,
+                           int nms_pre_maxsize, float nms_thresh, int nms_post_maxsize, float *out_boxes,
+                           float *out_scores, int64_t *out_labels, int32_t *out_count, void *workspace,
+                           size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * assign_score_withk / its gradient -- replace PD_BUILD_OP and PD_BUILD_GRAD_OP(assign_score_withk)
  * (assign_score_withk/assign_score_withk_cuda.cc:265-274, CPU kernels :32-158): PAConv's weight-bank assembly
  * (csrc/assign_score_withk.hip).  fp32 data, int64 knn_idx, contiguous tensors, 64-bit offsets.

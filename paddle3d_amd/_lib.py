@@ -229,6 +229,22 @@ _SIGNATURES = {
 
 SYMBOLS = tuple(_SIGNATURES)
 
+# Voxel R-CNN's RoI head (csrc/roi_head.hip).  A table of its own ON PURPOSE: tests/test_memory_safety_gpu.py fails for
+# any name in SYMBOLS that has no scenario in that file, and these entry points have theirs in
+# tests/test_memory_safety_roi_gpu.py, which ends in the same completeness assertion over SYMBOLS_ROI.
+_SIGNATURES_ROI = {
+    "pd3_voxel_pool": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 7 + [C.c_float] + [C.c_int] * 5 + [C.c_void_p] * 2),
+    "pd3_roi_grid_points": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int] +
+                            [C.c_void_p] * 3),
+    "pd3_rcnn_decode_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "pd3_class_agnostic_nms_workspace": (C.c_size_t, [C.c_int, C.c_int64, C.c_int]),
+    "pd3_class_agnostic_nms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_float,
+                                         C.c_void_p, C.c_int, C.c_float, C.c_int] + [C.c_void_p] * 5 +
+                               [C.c_size_t, C.c_void_p]),
+}
+
+SYMBOLS_ROI = tuple(_SIGNATURES_ROI)
+
 
 class Paddle3DAmdError(RuntimeError):
     pass
@@ -241,7 +257,7 @@ def lib() -> C.CDLL:
             f"{LIB_PATH} not found: build it with `python -m paddle3d_amd.build` "
             "(there is no CPU / PyTorch fallback for the HIP ops)")
     handle = C.CDLL(LIB_PATH)
-    for name, (res, args) in _SIGNATURES.items():
+    for name, (res, args) in list(_SIGNATURES.items()) + list(_SIGNATURES_ROI.items()):
         try:
             fn = getattr(handle, name)
         except AttributeError as e:  # pragma: no cover

@@ -12,8 +12,11 @@ voxel_query(max_range, radius, nsample, xyz, new_xyz, new_coords, point_indices)
 VoxelQueryAndGrouping(max_range, radius, nsample)
                                                voxel_query_utils.py:28-106: the voxel query, its global indices made
                                                frame-local on the device, grouping of xyz and features.
-NeighborVoxelSAModuleMSG(query_ranges, radii, nsamples, mlps, use_xyz, pool_method)
-                                               voxel_pool_modules.py:29-163.
+NeighborVoxelSAModuleMSG(query_ranges, radii, nsamples, mlps, use_xyz, pool_method, fused=False)
+                                               voxel_pool_modules.py:29-163.  fused=True: in eval mode without
+                                               gradients, a scale whose (C1, nsample) the op takes runs from the voxel
+                                               query to the pool as ops.roi_head.voxel_pool (no [M, *, nsample] tensor);
+                                               every other case runs the unfused forward.
 generate_voxel2pinds(sparse_tensor_shape, sparse_tensor_indices, n_dev=None)
                                                box_utils.py:102-110: [B, Z, Y, X] int32 row index per cell, -1 where
                                                a cell is empty.
@@ -30,7 +33,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from .ops import pointnet2_ops
+from .ops import pointnet2_ops, roi_head
 
 __all__ = ["QueryAndGroup", "StackSAModuleMSG", "build_local_aggregation_module", "voxel_query",
            "VoxelQueryAndGrouping", "NeighborVoxelSAModuleMSG", "generate_voxel2pinds"]
@@ -172,9 +175,10 @@ class VoxelQueryAndGrouping(nn.Module):
 
 class NeighborVoxelSAModuleMSG(nn.Module):
     def __init__(self, *, query_ranges, radii: List[float], nsamples: List[int], mlps: List[List[int]],
-                 use_xyz: bool = True, pool_method: str = "max_pool"):
+                 use_xyz: bool = True, pool_method: str = "max_pool", fused: bool = False):
         super().__init__()
         assert len(query_ranges) == len(nsamples) == len(mlps)
+        self.fused = fused
         self.groupers = nn.ModuleList()
         self.mlps_in = nn.ModuleList()
         self.mlps_pos = nn.ModuleList()
@@ -191,6 +195,23 @@ class NeighborVoxelSAModuleMSG(nn.Module):
         self.pool_method = pool_method
         _init_weights(self)
 
+    def _takes_fused(self, k):
+        g = self.groupers[k]
+        return (self.fused and not self.training and not torch.is_grad_enabled()
+                and self.pool_method in roi_head.POOLS
+                and roi_head.voxel_pool_supported(self.mlps_pos[k][0].out_channels, g.nsample))
+
+    def _fused_pool(self, k, new_xyz, new_coords, xyz, features_in, voxel2point_indices):
+        """[M, C1]: scale k from the voxel query to the pool in one kernel; mlps_pos as its conv weight and its
+        BatchNorm in eval form, scale = gamma / sqrt(var + eps), shift = beta - mean * scale, formed in fp32."""
+        conv, bn = self.mlps_pos[k][0], self.mlps_pos[k][1]
+        scale = bn.weight / torch.sqrt(bn.running_var + bn.eps)
+        shift = bn.bias - bn.running_mean * scale
+        g = self.groupers[k]
+        return roi_head.voxel_pool(new_xyz, new_coords, xyz, voxel2point_indices, features_in,
+                                   conv.weight.reshape(conv.out_channels, 3), scale, shift, g.max_range, g.radius,
+                                   g.nsample, self.pool_method)
+
     def forward(self, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, new_coords, features, voxel2point_indices):
         """xyz [N, 3] voxel centres, features [N, C], new_xyz [M, 3], new_coords [M, 4] as (b, x, y, z),
         voxel2point_indices [B, Z, Y, X] -> new_features [M, sum of mlps[k][2]]."""
@@ -200,6 +221,11 @@ class NeighborVoxelSAModuleMSG(nn.Module):
         for k, grouper in enumerate(self.groupers):
             features_in = self.mlps_in[k](features.transpose(0, 1).unsqueeze(0))  # [1, C1, N]
             features_in = features_in.transpose(1, 2).reshape(-1, int(features_in.shape[1]))  # [N, C1]
+            if self._takes_fused(k):
+                pooled = self._fused_pool(k, new_xyz, new_coords, xyz, features_in, voxel2point_indices)
+                new_features = self.mlps_out[k](pooled.transpose(0, 1).unsqueeze(0))  # [1, C2, M]
+                out.append(new_features.squeeze(0).transpose(0, 1))
+                continue
             grouped_features, grouped_xyz, empty = grouper(new_coords, xyz, xyz_batch_cnt, new_xyz,
                                                            new_xyz_batch_cnt, features_in, voxel2point_indices)
             grouped_features = grouped_features.masked_fill(empty[:, None, None], 0.0)

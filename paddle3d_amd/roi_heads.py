@@ -1,0 +1,269 @@
+"""Voxel R-CNN's second stage at inference on the device ops of paddle3d_amd/ops/roi_head.py.
+
+ResidualCoder(code_size=7)                     utils/box_coder.py:22-100, decode only (no sin / cos angle code).
+class_agnostic_nms(box_preds, cls_preds, nms_config, score_thresh, apply_sigmoid, labels)
+                                               models/common/model_nms_utils.py:20-66 for every frame in one call:
+                                               padded (boxes, scores, labels, count).
+RoIHeadBase(num_class, model_cfg)              heads/roi_heads/roi_head_base.py: proposal_layer (:70-131),
+                                               get_global_grid_points_of_roi (:324-346), generate_predicted_boxes
+                                               (:293-322).
+VoxelRCNNHead(input_channels, model_cfg, point_cloud_range, voxel_size, num_class)
+                                               heads/roi_heads/voxelrcnn_head.py:30-288 with the reference's
+                                               constructor arguments and sublayer names (roi_grid_pool_layers,
+                                               shared_fc_layer, cls_fc_layers, cls_pred_layer, reg_fc_layers,
+                                               reg_pred_layer), so checkpoint.load_paddle_state_dict maps a Paddle state
+                                               dict onto it.  forward(batch_dict): batch_size, batch_box_preds,
+                                               batch_cls_preds, multi_scale_3d_features (SparseConvTensor per source,
+                                               as SparseNet3D.forward returns them), multi_scale_3d_strides -> rois,
+                                               roi_scores, roi_labels, batch_cls_preds, batch_box_preds,
+                                               cls_preds_normalized.
+post_processing(batch_dict, post_process_cfg, num_class, padded=False)
+                                               detection/voxel_rcnn/voxel_rcnn.py:145-220: per frame box3d_lidar,
+                                               scores, label_preds.
+voxel_rcnn_head_kitti_car()                    the head of configs/voxel_rcnn/voxel_rcnn_005voxel_kitti_car.yml.
+
+Inference only: training (targets, losses) raises.  Dropout is the identity at inference and is left out of the
+Sequentials' arithmetic but kept in their numbering, so the Paddle sublayer indices hold.  Nothing in forward
+synchronises with the host: the per-frame voxel counts are a device bincount, the voxel-to-row map takes the sparse
+tensor's n_dev.  post_processing reads the counts on the host only to cut the tensors (padded=False).
+"""
+from __future__ import annotations
+
+import copy
+
+import numpy as np
+import torch
+from torch import nn
+
+from .ops import roi_head as _ops
+from .pointnet2_stack import NeighborVoxelSAModuleMSG, generate_voxel2pinds
+
+__all__ = ["ResidualCoder", "class_agnostic_nms", "RoIHeadBase", "VoxelRCNNHead", "post_processing",
+           "voxel_rcnn_head_kitti_car", "FUSED_POOL_DEFAULT"]
+
+# Whether VoxelRCNNHead builds its pool layers with the fused voxel pool (DESIGN 4.5h has the measurement behind it).
+FUSED_POOL_DEFAULT = True
+
+
+class ResidualCoder:
+    def __init__(self, code_size=7, encode_angle_by_sincos=False, **kwargs):
+        if encode_angle_by_sincos:
+            raise NotImplementedError("ResidualCoder: encode_angle_by_sincos")
+        if code_size != 7:
+            raise NotImplementedError(f"ResidualCoder: code_size {code_size}")
+        self.code_size = code_size
+        self.encode_angle_by_sincos = False
+
+
+def class_agnostic_nms(box_preds, cls_preds, nms_config, score_thresh=None, apply_sigmoid=False, labels=None):
+    """box_preds [B, A, 7], cls_preds [B, A, K] -> (boxes [B, post, 7], scores [B, post], labels [B, post] int64
+    0-based (or `labels`' entries), count [B] int32); rows behind a frame's count are zeros, a frame that passes
+    nothing under score_thresh has the reference's box_empty row (score -1, label -1) in row 0 and count 0."""
+    if nms_config.get("multi_class_nms", False) or nms_config.get("multi_classes_nms", False):
+        raise NotImplementedError("multi-class NMS (the reference raises as well)")
+    return _ops.class_agnostic_nms(box_preds, cls_preds, nms_config, score_thresh=score_thresh,
+                                   apply_sigmoid=apply_sigmoid, labels=labels)
+
+
+class RoIHeadBase(nn.Module):
+    def __init__(self, num_class, model_cfg, **kwargs):
+        super().__init__()
+        self.model_cfg = model_cfg
+        self.num_class = num_class
+        target = model_cfg.get("target_config", {})
+        if target.get("box_coder", "ResidualCoder") != "ResidualCoder":
+            raise NotImplementedError(target["box_coder"])
+        self.box_coder = ResidualCoder(**target.get("box_coder_config", {}))
+
+    @torch.no_grad()
+    def proposal_layer(self, batch_dict, nms_config):
+        """rois [B, post, 7], roi_scores [B, post], roi_labels [B, post] int64 (1-based; padded rows read 1, as the
+        reference's `+ 1` on its zero-padded tensor leaves them)."""
+        if batch_dict.get("rois", None) is not None:
+            return batch_dict
+        if batch_dict.get("batch_index", None) is not None:
+            raise NotImplementedError("proposal_layer: stacked predictions with batch_index")
+        box_preds, cls_preds = batch_dict["batch_box_preds"], batch_dict["batch_cls_preds"]
+        assert cls_preds.dim() == 3 and int(box_preds.shape[0]) == int(batch_dict["batch_size"])
+        rois, scores, labels, _ = class_agnostic_nms(box_preds, cls_preds, nms_config)
+        batch_dict["rois"] = rois
+        batch_dict["roi_scores"] = scores
+        batch_dict["roi_labels"] = labels + 1
+        return batch_dict
+
+    def get_global_grid_points_of_roi(self, rois, grid_size):
+        """rois [B, R, 7] -> global grid points [B * R, G^3, 3]."""
+        xyz, _ = _ops.roi_grid_points(rois, grid_size, (0.0, 0.0, 0.0), (1.0, 1.0, 1.0), [])
+        return xyz.view(-1, int(grid_size) ** 3, 3)
+
+    def generate_predicted_boxes(self, batch_size, rois, cls_preds, box_preds):
+        """rois [B, R, 7], cls_preds [B * R, K], box_preds [B * R, 7] -> (batch_cls_preds [B, R, K], batch_box_preds
+        [B, R, 7])."""
+        batch_cls_preds = cls_preds.reshape(batch_size, -1, int(cls_preds.shape[-1]))
+        return batch_cls_preds, _ops.rcnn_decode_boxes(rois, box_preds.reshape(batch_size, -1, 7))
+
+
+def _fc_stack(pre_channel, widths, dp_ratio):
+    layers = []
+    for k, w in enumerate(widths):
+        layers += [nn.Linear(pre_channel, w, bias=False), nn.BatchNorm1d(w), nn.ReLU()]
+        pre_channel = w
+        if k != len(widths) - 1 and dp_ratio > 0:
+            layers.append(nn.Identity())  # the reference's Dropout: identity at inference, holds the sublayer index
+    return nn.Sequential(*layers), pre_channel
+
+
+class VoxelRCNNHead(RoIHeadBase):
+    def __init__(self, input_channels, model_cfg, point_cloud_range, voxel_size, num_class=1, fused_pool=None,
+                 **kwargs):
+        model_cfg = copy.deepcopy(model_cfg)  # the reference prepends the input channels to cfg["mlps"] in place
+        super().__init__(num_class=num_class, model_cfg=model_cfg)
+        self.pool_cfg = model_cfg["roi_grid_pool"]
+        layer_cfg = self.pool_cfg["pool_layers"]
+        self.point_cloud_range = [float(v) for v in point_cloud_range]
+        self.voxel_size = [float(v) for v in voxel_size]
+        fused = FUSED_POOL_DEFAULT if fused_pool is None else bool(fused_pool)
+
+        c_out = 0
+        self.roi_grid_pool_layers = nn.ModuleList()
+        for src_name in self.pool_cfg["features_source"]:
+            cfg = layer_cfg[src_name]
+            mlps = [[input_channels[src_name]] + list(m) for m in cfg["mlps"]]
+            self.roi_grid_pool_layers.append(NeighborVoxelSAModuleMSG(
+                query_ranges=cfg["query_ranges"], nsamples=cfg["nsample"], radii=cfg["pool_radius"], mlps=mlps,
+                pool_method=cfg["pool_method"], fused=fused))
+            c_out += sum(x[-1] for x in mlps)
+
+        grid = int(self.pool_cfg["grid_size"])
+        dp = model_cfg["dp_ratio"]
+        self.shared_fc_layer, pre = _fc_stack(grid ** 3 * c_out, model_cfg["shared_fc"], dp)
+        self.cls_fc_layers, pre_cls = _fc_stack(pre, model_cfg["cls_fc"], dp)
+        self.cls_pred_layer = nn.Linear(pre_cls, self.num_class, bias=True)
+        # as the reference: the regression stack's input width is where the classification stack ended
+        # (voxelrcnn_head.py:89-101), so shared_fc[-1] == cls_fc[-1] for a head that runs
+        self.reg_fc_layers, pre_reg = _fc_stack(pre_cls, model_cfg["reg_fc"], dp)
+        self.reg_pred_layer = nn.Linear(pre_reg, self.box_coder.code_size * self.num_class, bias=True)
+        self.init_weights()
+
+    def init_weights(self):
+        for stack in (self.shared_fc_layer, self.cls_fc_layers, self.reg_fc_layers):
+            for m in stack.modules():
+                if isinstance(m, nn.Linear):
+                    nn.init.xavier_normal_(m.weight)
+                elif isinstance(m, nn.BatchNorm1d):
+                    nn.init.ones_(m.weight)
+                    nn.init.zeros_(m.bias)
+        nn.init.normal_(self.cls_pred_layer.weight, mean=0.0, std=0.01)
+        nn.init.zeros_(self.cls_pred_layer.bias)
+        nn.init.normal_(self.reg_pred_layer.weight, mean=0.0, std=0.001)
+        nn.init.zeros_(self.reg_pred_layer.bias)
+
+    def roi_grid_pool(self, batch_dict):
+        """-> pooled features [B * R, G^3, C]."""
+        rois = batch_dict["rois"]
+        batch_size = int(batch_dict["batch_size"])
+        grid = int(self.pool_cfg["grid_size"])
+        sources = list(self.pool_cfg["features_source"])
+        strides = [int(batch_dict["multi_scale_3d_strides"][s]) for s in sources]
+        roi_grid_xyz, coords = _ops.roi_grid_points(rois, grid, self.point_cloud_range, self.voxel_size, strides)
+        per_frame = int(rois.shape[1]) * grid ** 3
+        roi_grid_batch_cnt = torch.full((batch_size,), per_frame, dtype=torch.int32, device=rois.device)
+        pooled = []
+        for k, src_name in enumerate(sources):
+            sp = batch_dict["multi_scale_3d_features"][src_name]
+            ind = sp.indices  # [N, 4] (b, z, y, x)
+            N = int(ind.shape[0])
+            rows = torch.arange(N, dtype=torch.int32, device=ind.device)
+            valid = rows >= 0 if sp.n_dev is None else rows < sp.n_dev.reshape(-1)[:1].to(torch.int32)
+            # get_voxel_centers (box_utils.py:76-99): (coords_xyz + 0.5) * (voxel_size * stride) + range_min in fp32,
+            # column by column with host scalars (a list copied to the device would synchronise)
+            cols = []
+            for a, col in enumerate((3, 2, 1)):  # x, y, z
+                size = float(np.float32(self.voxel_size[a]) * np.float32(strides[k]))
+                lo = float(np.float32(self.point_cloud_range[a]))
+                cols.append((ind[:, col].to(torch.float32) + 0.5) * size + lo)
+            xyz = torch.stack(cols, dim=1)
+            b = ind[:, 0].long()
+            slot = torch.where(valid & (b >= 0) & (b < batch_size), b, torch.full_like(b, batch_size))
+            cnt = torch.zeros(batch_size + 1, dtype=torch.int32, device=ind.device)
+            cnt.index_add_(0, slot, torch.ones_like(rows))
+            v2p = generate_voxel2pinds([batch_size, *sp.spatial_shape, int(sp.features.shape[1])], ind, sp.n_dev)
+            feats = self.roi_grid_pool_layers[k](
+                xyz=xyz, xyz_batch_cnt=cnt[:batch_size], new_xyz=roi_grid_xyz, new_xyz_batch_cnt=roi_grid_batch_cnt,
+                new_coords=coords[k], features=sp.features.float(), voxel2point_indices=v2p)
+            pooled.append(feats.reshape(-1, grid ** 3, int(feats.shape[-1])))
+        return torch.cat(pooled, dim=-1)
+
+    def forward(self, batch_dict):
+        if self.training:
+            raise NotImplementedError("VoxelRCNNHead: inference only (targets and losses are not built)")
+        self.proposal_layer(batch_dict, nms_config=self.model_cfg["nms_config"]["test"])
+        pooled = self.roi_grid_pool(batch_dict)
+        pooled = pooled.reshape(int(pooled.shape[0]), -1)
+        shared = self.shared_fc_layer(pooled)
+        rcnn_cls = self.cls_pred_layer(self.cls_fc_layers(shared))
+        rcnn_reg = self.reg_pred_layer(self.reg_fc_layers(shared))
+        batch_cls_preds, batch_box_preds = self.generate_predicted_boxes(
+            batch_size=int(batch_dict["batch_size"]), rois=batch_dict["rois"], cls_preds=rcnn_cls, box_preds=rcnn_reg)
+        batch_dict["batch_cls_preds"] = batch_cls_preds
+        batch_dict["batch_box_preds"] = batch_box_preds
+        batch_dict["cls_preds_normalized"] = False
+        return batch_dict
+
+
+@torch.no_grad()
+def post_processing(batch_dict, post_process_cfg, num_class, padded=False):
+    """VoxelRCNN.post_processing.  padded=False: a list of {box3d_lidar, scores, label_preds} per frame, cut to the
+    frame's count (one host read of the counts; a frame that passed nothing is the reference's box_empty row).
+    padded=True: (boxes [B, post, 7], scores [B, post], labels [B, post], count [B]) without a host read."""
+    if batch_dict.get("batch_index", None) is not None or isinstance(batch_dict["batch_cls_preds"], list):
+        raise NotImplementedError("post_processing: stacked or multi-head predictions")
+    cls_preds, box_preds = batch_dict["batch_cls_preds"], batch_dict["batch_box_preds"]
+    assert int(cls_preds.shape[-1]) in (1, num_class)
+    labels_in = None
+    if num_class > 1:
+        key = "roi_labels" if "roi_labels" in batch_dict else "batch_pred_labels"
+        labels_in = batch_dict[key].reshape(int(box_preds.shape[0]), -1).long()
+    boxes, scores, labels, count = class_agnostic_nms(
+        box_preds, cls_preds, post_process_cfg["nms_config"], score_thresh=post_process_cfg["score_thresh"],
+        apply_sigmoid=not batch_dict["cls_preds_normalized"], labels=labels_in)
+    if labels_in is None:  # the reference's `label_preds + 1`; the box_empty row keeps its -1
+        rows = torch.arange(int(labels.shape[1]), device=labels.device)[None, :]
+        labels = torch.where(rows < count[:, None], labels + 1, labels)
+    if padded:
+        return boxes, scores, labels, count
+    out = []
+    for b, n in enumerate(count.tolist()):  # the host read
+        if n == 0 and post_process_cfg["score_thresh"] is not None:
+            n = 1  # the box_empty row
+        out.append({"box3d_lidar": boxes[b, :n], "scores": scores[b, :n], "label_preds": labels[b, :n]})
+    return out
+
+
+KITTI_CAR_MODEL_CFG = {
+    "class_agnostic": True, "shared_fc": [256, 256], "cls_fc": [256, 256], "reg_fc": [256, 256], "dp_ratio": 0.3,
+    "nms_config": {
+        "train": {"nms_type": "nms_gpu", "multi_class_nms": False, "nms_pre_maxsize": 9000, "nms_post_maxsize": 512,
+                  "nms_thresh": 0.8},
+        "test": {"nms_type": "nms_gpu", "multi_class_nms": False, "use_fast_nms": False, "score_thresh": 0.0,
+                 "nms_pre_maxsize": 2048, "nms_post_maxsize": 100, "nms_thresh": 0.7}},
+    "roi_grid_pool": {
+        "features_source": ["x_conv2", "x_conv3", "x_conv4"], "pre_mlp": True, "grid_size": 6,
+        "pool_layers": {
+            "x_conv2": {"mlps": [[32, 32]], "query_ranges": [[4, 4, 4]], "pool_radius": [0.4], "nsample": [16],
+                        "pool_method": "max_pool"},
+            "x_conv3": {"mlps": [[32, 32]], "query_ranges": [[4, 4, 4]], "pool_radius": [0.8], "nsample": [16],
+                        "pool_method": "max_pool"},
+            "x_conv4": {"mlps": [[32, 32]], "query_ranges": [[4, 4, 4]], "pool_radius": [1.6], "nsample": [16],
+                        "pool_method": "max_pool"}}},
+    "target_config": {"box_coder": "ResidualCoder"},
+}
+KITTI_CAR_POST_PROCESS_CFG = {"score_thresh": 0.3, "output_raw_score": False,
+                              "nms_config": {"multi_classes_nms": False, "nms_type": "nms_gpu", "nms_thresh": 0.1,
+                                             "nms_pre_maxsize": 4096, "nms_post_maxsize": 500}}
+
+
+def voxel_rcnn_head_kitti_car(fused_pool=None):
+    return VoxelRCNNHead(input_channels={"x_conv1": 16, "x_conv2": 32, "x_conv3": 64, "x_conv4": 64},
+                         model_cfg=KITTI_CAR_MODEL_CFG, point_cloud_range=[0, -40, -3, 70.4, 40, 1],
+                         voxel_size=[0.05, 0.05, 0.1], num_class=1, fused_pool=fused_pool)
