@@ -653,7 +653,7 @@ class SecondFPN(_InferenceCache, nn.Module):
                 raise Paddle3DAmdError(f"patch_conv: unsupported configuration (mode {p['mode']} on a map of width "
                                        f"{_valid_w(x)}, not a multiple of 4) (status -3)")
             if _conv.PATCH_BF16X3 and _conv.patch_x3_supported(p["mode"], p["cin"], p["cout"], int(x.shape[2]),
-                                                               int(x.shape[3])):
+                                                               int(x.shape[3]), int(x.shape[0]), ctot):
                 # fp32 arithmetic on the bf16 matrix cores (three pieces per operand, csrc/conv_patch_x3.hip)
                 if "wx3" not in p:
                     p["wx3"] = _conv.pack_patch_weight_x3(p["wraw"], p["mode"], p["tr"])

@@ -241,15 +241,26 @@ def patch_conv_bias_relu(x: torch.Tensor, w_packed: torch.Tensor, bias, mode: in
 PATCH_BF16X3 = True
 
 
-def patch_x3_supported(mode: int, cin: int, cout: int, h: int, w: int) -> bool:
-    """pd3_patch_conv_x3_bias_relu's shapes ([h, w] = input map, w its row pitch)."""
+def patch_x3_supported(mode: int, cin: int, cout: int, h: int, w: int, batch: int = 1, ctot: int | None = None) -> bool:
+    """pd3_patch_conv_x3_bias_relu's shapes ([h, w] = input map, w its row pitch; ctot = channels of the output the
+    level is written into, default cout).  Like conv3x3_s2_x3_supported: the layer's bias sits in LDS (cout <= 1024) and
+    the kernel addresses x, out and the weights with 32-bit byte offsets (each below 0x7ffffff0 bytes)."""
     if mode == 0:
-        return cin % 16 == 0 and cout % 128 == 0 and h % 2 == 0 and w % 64 == 0
-    if mode == 1:
-        return cin % 32 == 0 and cout % 128 == 0 and (h * w) % 4 == 0
-    if mode == 2:
-        return cin % 32 == 0 and cout % 64 == 0 and (h * w) % 4 == 0
-    return False
+        ok, out_px = cin % 16 == 0 and cout % 128 == 0 and h % 2 == 0 and w % 64 == 0, (h // 2) * (w // 2)
+    elif mode == 1:
+        ok, out_px = cin % 32 == 0 and cout % 128 == 0 and (h * w) % 4 == 0, h * w
+    elif mode == 2:
+        ok, out_px = cin % 32 == 0 and cout % 64 == 0 and (h * w) % 4 == 0, 4 * h * w
+    else:
+        return False
+    if not ok or cout > 1024:
+        return False
+    ctot = cout if ctot is None else int(ctot)
+    steps = 2 * (cin // 16) if mode == 0 else cin // 32   # 32 KB of weight pieces per (128-row tile, step)
+    tiles = 2 * (cout // 64) if mode == 2 else cout // 128
+    ptiles = batch * -(-min(out_px, h * w) // 256)        # 256-pixel tiles of the plane the kernel walks
+    return (batch * cin * h * w * 4 < 0x7ffffff0 and batch * ctot * out_px * 4 < 0x7ffffff0
+            and tiles * steps * 32768 < 0x7ffffff0 and ptiles < 1 << 28)
 
 
 def split_bf16x3(a: torch.Tensor) -> torch.Tensor:
@@ -493,12 +504,14 @@ def scatter_conv_s2_f16_supported(cin: int, cout: int, ny: int, nx: int) -> bool
 
 def scatter_conv3x3_s2_f16_bias_relu(canvas, w_packed: torch.Tensor, bias, cout: int, relu: bool = True) -> torch.Tensor:
     """scatter_conv3x3_bias_relu on the fp16 matrix cores: a SparseCanvas (pillar features converted to fp16 once, the
-    inverse map) -> [B, ny / 2, nx / 2, cout] fp16 NHWC; w_packed = pack_conv3x3_f16_weight(weight, tile=64 | 128)."""
+    inverse map) -> [B, (ny - 1) // 2 + 1, (nx - 1) // 2 + 1, cout] fp16 NHWC (the kernel's own output size, as
+    conv3x3_s2_f16_bias_relu: an odd canvas has one more row / column than ny // 2); w_packed =
+    pack_conv3x3_f16_weight(weight, tile=64 | 128)."""
     f, inv = canvas.features, canvas.inv
     fh = f if f.dtype == torch.float16 else f.half()
     n, cin, ny, nx = canvas.shape
     tile = int(w_packed.shape[4])
-    out = torch.empty((n, ny // 2, nx // 2, cout), dtype=torch.float16, device=f.device)
+    out = torch.empty((n, (ny - 1) // 2 + 1, (nx - 1) // 2 + 1, cout), dtype=torch.float16, device=f.device)
     check(lib().pd3_scatter_conv3x3_s2_f16_bias_relu(ptr(fh), ptr(inv), ptr(w_packed), ptr(bias), n, cin, cout, ny, nx,
                                                      int(bool(relu)), ptr(out), tile, stream_ptr(f.device)),
           "scatter_conv3x3_s2_f16_bias_relu")
