@@ -306,27 +306,36 @@ class _Conv3x3:
         self.cout, self.cin = int(w.shape[0]), int(w.shape[1])
         self.packed = {}
 
+    def winograd43(self, h, pitch):
+        """Which F(4x4,3x3) form runs this layer at (h, pitch) -- "pp" (ping-pong) or "packed" -- and that form's packed
+        weight (packed on first use, [cout / T][...] in both packings); (None, None) where neither takes the layer."""
+        if self.stride != 1:
+            return None, None
+        if self.cin >= _conv.WINOGRAD43_PP_MIN_CIN and _conv.winograd43_pp_supported(self.cin, self.cout, h, pitch):
+            # the ping-pong form: the same bytes as the packed form, 2-9 % faster on this model's layers (DESIGN 4.6)
+            form, key, pack = "pp", "w43pp", _conv.pack_winograd43_lane_weight
+        elif _conv.winograd43_supported(self.cin, self.cout, h, pitch):
+            form, key, pack = "packed", "w43", _conv.pack_winograd43_weight
+        else:
+            return None, None
+        if key not in self.packed:
+            self.packed[key] = pack(self.w)
+        return form, self.packed[key]
+
     def __call__(self, x, w_valid=None):
         """x [n, cin, h, pitch]; w_valid = its real width (default pitch; a width that is not a multiple of 4 lives in
         zero-padded rows, ops/conv.py:pitch4).  Returns (y, real width of y)."""
         h, wv = int(x.shape[2]), int(x.shape[3] if w_valid is None else w_valid)
-        if (self.stride == 1 and self.cin >= _conv.WINOGRAD43_PP_MIN_CIN
-                and _conv.winograd43_pp_supported(self.cin, self.cout, h, int(x.shape[3]))):
-            # the ping-pong form: the same bytes as the packed form, 2-9 % faster on this model's layers (DESIGN 4.6)
-            if "w43pp" not in self.packed:
-                self.packed["w43pp"] = _conv.pack_winograd43_lane_weight(self.w)
+        form, u = self.winograd43(h, int(x.shape[3]))
+        if form == "pp":
             if 0 < _conv.WINOGRAD43_PPV_MIN_BLOCKS <= self.cout // 64:
                 # enough channel blocks over this input to compute its Winograd transform once for all of them (round 6)
                 vpre = _conv.winograd43_input_transform(x, w_valid=wv)
-                return _conv.conv3x3_winograd43_ppv_bias_relu(vpre, x.shape, self.packed["w43pp"], self.b, self.cout,
-                                                              relu=True, w_valid=wv), wv
-            return _conv.conv3x3_winograd43_pp_bias_relu(x, self.packed["w43pp"], self.b, self.cout, relu=True,
-                                                         w_valid=wv), wv
-        if self.stride == 1 and _conv.winograd43_supported(self.cin, self.cout, h, wv):
-            if "w43" not in self.packed:
-                self.packed["w43"] = _conv.pack_winograd43_weight(self.w)
-            return _conv.conv3x3_winograd43_bias_relu(x, self.packed["w43"], self.b, self.cout, relu=True,
-                                                      w_valid=wv), wv
+                return _conv.conv3x3_winograd43_ppv_bias_relu(vpre, x.shape, u, self.b, self.cout, relu=True,
+                                                              w_valid=wv), wv
+            return _conv.conv3x3_winograd43_pp_bias_relu(x, u, self.b, self.cout, relu=True, w_valid=wv), wv
+        if form == "packed":
+            return _conv.conv3x3_winograd43_bias_relu(x, u, self.b, self.cout, relu=True, w_valid=wv), wv
         if (self.stride == 2 and _conv.S2_BF16X3 and int(x.shape[3]) % 4 == 0
                 and _conv.conv3x3_s2_x3_supported(self.cin, self.cout, h, wv, int(x.shape[0]))):
             # fp32 arithmetic on the bf16 matrix cores (three pieces per operand, csrc/conv_s2_x3.hip)
@@ -804,20 +813,11 @@ class CenterHead(_InferenceCache, nn.Module):
             # the shared map in the reference's layout and dtype in both modes (center_head.py:212-220 returns
             # `ret_dicts, x` with x fp32 [n, 64, h, w]); one 16 MB elementwise pass per 16 frames
             return rets, (x.permute(0, 3, 1, 2).float() if want_shared else None)
-        chunked = (k < groups and f["hc"] == 64 and first.stride == 1 and _conv.winograd43_supported(first.cin, first.cout, h, w)
-                   and w % 4 == 0)
-        if chunked:
-            pp = first.cin >= _conv.WINOGRAD43_PP_MIN_CIN and _conv.winograd43_pp_supported(first.cin, first.cout, h, w)
-            if pp:  # [cout / 64][...]: channel tiles are slices of the first dimension in both packings
-                if "w43pp" not in first.packed:
-                    first.packed["w43pp"] = _conv.pack_winograd43_lane_weight(first.w)
-                u = first.packed["w43pp"]
-            else:
-                if "w43" not in first.packed:
-                    first.packed["w43"] = _conv.pack_winograd43_weight(first.w)
-                u = first.packed["w43"]
-                chunked = int(u.shape[2]) * 16 == 64
-        if chunked:
+        # [cout / 64][...]: channel tiles are slices of the first dimension in both packings (the packed form: where
+        # it runs with 64 channels per workgroup)
+        form, u = first.winograd43(h, w) if k < groups and f["hc"] == 64 and w % 4 == 0 else (None, None)
+        pp = form == "pp"
+        if pp or (form == "packed" and int(u.shape[2]) * 16 == 64):
             wino = _conv.conv3x3_winograd43_pp_bias_relu if pp else _conv.conv3x3_winograd43_bias_relu
             z = torch.empty((n, groups * f["cmax"], h, w), dtype=torch.float32, device=x.device)
             buf = torch.empty((n * k * 64 * h * w,), dtype=torch.float32, device=x.device)

@@ -52,14 +52,9 @@ __global__ __launch_bounds__(128 * CB, CB == 2 ? 2 : 1) void conv3x3_winograd43_
   float* Raw = Vs + NBUF * kW4Vsz;
   float *Ucur = Us, *Vcur = Vs, *Unext = Us, *Vnext = Vs;  // buffers of the trip being multiplied / prepared
   const int lane = lane_id(), wave = wave_id();
-  const int tiles_x = (w + 4 * kW4TC - 1) / (4 * kW4TC), tiles_y = (h + 4 * kW4TR - 1) / (4 * kW4TR);
-  // XCD-aware tile order (see conv_winograd.hip): pixel tile pt lives on XCD pt % 8 with all its channel tiles
-  const int nct = cout / CO;
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-  const int ct = slot % nct, pt = (slot / nct) * 8 + xcd;
-  if (pt >= ptiles) return;
-  const int tx = pt % tiles_x, ty = (pt / tiles_x) % tiles_y, n = pt / (tiles_x * tiles_y);
-  const int y0 = ty * 4 * kW4TR, x0 = tx * 4 * kW4TC;
+  const w4_tile tl = w4_decode_block(cout / CO, h, w);
+  if (tl.pt >= ptiles) return;
+  const int ct = tl.cg, n = tl.n, y0 = tl.y0, x0 = tl.x0;
   const int chunks = cin / kW4Ci;
   const int64_t plane = (int64_t)h * w;
   const float* xin = x + (int64_t)n * cin * plane;
@@ -124,57 +119,22 @@ __global__ __launch_bounds__(128 * CB, CB == 2 ? 2 : 1) void conv3x3_winograd43_
     _Pragma("unroll") for (int i = 0; i < UPT; ++i)                                      \
         *reinterpret_cast<w4_f32x4*>(Unext + uofs[i] * 4) = ur[i];                       \
   }
-  // V = B^T d B.  Row pass on this lane's three columns, halves swapped between the pair, column pass on this
-  // lane's three rows; components (row, nu) -> 6 row + nu.
-#define W4_TRANSFORM()                                                                   \
-  if (CB == 2 || transforms) {                                                                                      \
-    float lo_[3][3], hi_[3][3]; /* (B^T d)[row a or 3 + a][my column b] */               \
-    _Pragma("unroll") for (int b = 0; b < 3; ++b) {                                      \
-      const float* d_ = Raw + rsrc + b;                                                  \
-      float t_[6];                                                                       \
-      w4_in(d_[0], d_[kW4RawW], d_[2 * kW4RawW], d_[3 * kW4RawW], d_[4 * kW4RawW], d_[5 * kW4RawW], t_); \
-      _Pragma("unroll") for (int a = 0; a < 3; ++a) {                                    \
-        lo_[a][b] = t_[a];                                                               \
-        hi_[a][b] = t_[3 + a];                                                           \
-      }                                                                                  \
-    }                                                                                    \
-    /* the even lane runs the column pass for rows 0..2, the odd lane for rows 3..5; what a lane lacks are \
-       the other three columns of its rows, i.e. the partner's lo_ (even lane) or hi_ (odd lane): one      \
-       select with a DPP-swapped operand per value */                                    \
-    float* v_ = Vnext + vdst;                                                            \
-    _Pragma("unroll") for (int a = 0; a < 3; ++a) {                                      \
-      float f_[3], l_[3]; /* columns 0..2 / 3..5 of row 3 hf + a of B^T d */             \
-      _Pragma("unroll") for (int b = 0; b < 3; ++b) {                                    \
-        const float ph_ = w4_swap_pair(hi_[a][b]), pl_ = w4_swap_pair(lo_[a][b]);        \
-        f_[b] = hf ? ph_ : lo_[a][b];                                                    \
-        l_[b] = hf ? hi_[a][b] : pl_;                                                    \
-      }                                                                                  \
-      float o_[6];                                                                       \
-      w4_in(f_[0], f_[1], f_[2], l_[0], l_[1], l_[2], o_);                               \
-      *reinterpret_cast<w4_f32x2*>(v_ + a * 6 + 0) = (w4_f32x2){o_[0], o_[1]};           \
-      *reinterpret_cast<w4_f32x2*>(v_ + a * 6 + 2) = (w4_f32x2){o_[2], o_[3]};           \
-      *reinterpret_cast<w4_f32x2*>(v_ + a * 6 + 4) = (w4_f32x2){o_[4], o_[5]};           \
-    }                                                                                    \
-  }
-  // 9 groups of 4 components: two b128 reads feed four MFMAs; reads run two groups ahead (ring of three)
-#define W4_LOAD(g_, slot_)                                                               \
-  {                                                                                      \
-    a_[slot_] = *reinterpret_cast<const w4_f32x4*>(Ucur + abase + (g_) * 4);             \
-    b_[slot_] = *reinterpret_cast<const w4_f32x4*>(Vcur + bbase + (g_) * 4);             \
-  }
-#define W4_MFMA()                                                                        \
-  {                                                                                      \
-    w4_f32x4 a_[3], b_[3];                                                               \
-    W4_LOAD(0, 0)                                                                        \
-    W4_LOAD(1, 1)                                                                        \
-    _Pragma("unroll") for (int g_ = 0; g_ < 9; ++g_) {                                   \
-      if (g_ + 2 < 9) W4_LOAD(g_ + 2, (g_ + 2) % 3)                                      \
-      __builtin_amdgcn_sched_barrier(0);                                                 \
-      _Pragma("unroll") for (int j_ = 0; j_ < 4; ++j_)                                   \
-          acc[g_ * 4 + j_] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_[g_ % 3][j_], b_[g_ % 3][j_], acc[g_ * 4 + j_], 0, 0, 0); \
-      __builtin_amdgcn_sched_barrier(0);                                                 \
-    }                                                                                    \
-  }
+  // V = B^T d B of the pair's patch, from Raw to Vnext
+  auto transform = [&]() {
+    if (CB == 2 || transforms) {
+      float rv[3][6];
+#pragma unroll
+      for (int b = 0; b < 3; ++b)
+#pragma unroll
+        for (int r = 0; r < 6; ++r) rv[b][r] = Raw[rsrc + b + r * kW4RawW];
+      w4_pair_transform(rv, hf, Vnext + vdst);
+    }
+  };
+  // one trip: 9 groups of 4 components
+  auto multiply = [&]() {
+    w4_mfma_stream<9>(
+        acc, [&](int g) { return Ucur + abase + g * 4; }, [&](int g) { return Vcur + bbase + g * 4; });
+  };
 
   // The U slice of a trip is 37 KB (CB = 4): its loads back-pressure at issue for ~1700 cycles (the L2 -> CU
   // path delivers ~16 B/clk), and a wave issues in order -- so they are issued where their waves have slack, right
@@ -183,7 +143,7 @@ __global__ __launch_bounds__(128 * CB, CB == 2 ? 2 : 1) void conv3x3_winograd43_
   W4_FETCH_U(0)
   W4_STASH_X()
   __syncthreads();
-  W4_TRANSFORM()
+  transform();
   W4_STASH_U()
   if (chunks > 1) W4_FETCH_U(1)
   if (CB == 4 && chunks > 1) W4_FETCH_X(1)
@@ -208,13 +168,13 @@ __global__ __launch_bounds__(128 * CB, CB == 2 ? 2 : 1) void conv3x3_winograd43_
       }
       __syncthreads();
       if (transforms) {
-        if (more) W4_TRANSFORM()
+        if (more) transform();
         __builtin_amdgcn_s_setprio(1);
-        W4_MFMA()
+        multiply();
         __builtin_amdgcn_s_setprio(0);
       } else {
         __builtin_amdgcn_s_setprio(1);
-        W4_MFMA()
+        multiply();
         __builtin_amdgcn_s_setprio(0);
         if (more) W4_STASH_U()
         if (cc + 2 < chunks) W4_FETCH_U(cc + 2)
@@ -227,66 +187,33 @@ __global__ __launch_bounds__(128 * CB, CB == 2 ? 2 : 1) void conv3x3_winograd43_
       W4_FETCH_X(cc + 1)
       __builtin_amdgcn_sched_barrier(0);  // keep the loads in flight ahead of the MFMA block
       __builtin_amdgcn_s_setprio(1);  // the matrix phase outranks the co-resident waves' transform VALU
-      W4_MFMA()
+      multiply();
       __builtin_amdgcn_s_setprio(0);
       __builtin_amdgcn_sched_barrier(0);
       __syncthreads();  // every wave is done with U and V of this trip
       W4_STASH_X()
       __syncthreads();
-      W4_TRANSFORM()
+      transform();
       W4_STASH_U()
       if (cc + 2 < chunks) W4_FETCH_U(cc + 2)
       __syncthreads();
     }
-    W4_MFMA()
+    multiply();
   }
-#undef W4_MFMA
-#undef W4_LOAD
 #undef W4_FETCH_X
 #undef W4_FETCH_U
 #undef W4_STASH_X
 #undef W4_STASH_U
-#undef W4_TRANSFORM
 
-  // epilogue: Y = A^T M A; lane: tile column lane & 15, channels 4 (lane >> 4) + r of the co block
-  float bv[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) bv[r] = 0.f;
+  // epilogue: lane: tile column lane & 15, channels 4 (lane >> 4) + r of the co block
+  w4_f32x4 bv = {0.f, 0.f, 0.f, 0.f};
   const int co0 = ct * CO + cb * 16 + 4 * (lane >> 4);
   if (bias) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) bv[r] = bias[co0 + r];
   }
-  const int oy = y0 + 4 * tb, ox = x0 + 4 * (lane & 15);
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    float s[4][6];  // A^T M: column j of M through the row pass
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-      float c4[4];
-      w4_out(acc[0 * 6 + j][r], acc[1 * 6 + j][r], acc[2 * 6 + j][r], acc[3 * 6 + j][r], acc[4 * 6 + j][r],
-             acc[5 * 6 + j][r], c4);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) s[k][j] = c4[k];
-    }
-    float* o = out + ((int64_t)n * cout + co0 + r) * plane + (int64_t)oy * w + ox;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      float y4[4];
-      w4_out(s[k][0], s[k][1], s[k][2], s[k][3], s[k][4], s[k][5], y4);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        y4[j] += bv[r];
-        if (relu) y4[j] = fmaxf(y4[j], 0.f);
-        if (ox + j >= wv) y4[j] = 0.f;
-      }
-      if (oy + k < h && ox < w)  // partial tiles at the border (w % 4 == 0: a quad is in or out)
-        __builtin_nontemporal_store((w4_f32x4){y4[0], y4[1], y4[2], y4[3]},
-                                    reinterpret_cast<w4_f32x4*>(o + (int64_t)k * w));
-    }
-  }
+  w4_output_step(acc, bv, n, cout, co0, y0 + 4 * tb, x0 + 4 * (lane & 15), h, w, wv, relu, plane, out);
 }
-
 
 }  // namespace pd3
 
@@ -300,8 +227,8 @@ static int launch_wino43(const float* x, const float* u_packed, const float* bia
     hipError_t e = pd3_max_dynamic_lds(reinterpret_cast<const void*>(conv3x3_winograd43_kernel<CB>), (int)lds);
     if (e != hipSuccess) return (int)e;
   }
-  const int64_t ptiles = (int64_t)batch * ceil_div(h, 4 * kW4TR) * ceil_div(w, 4 * kW4TC);
-  const int64_t nwg = (ptiles + 7) / 8 * 8 * (cout / (16 * CB));
+  int64_t ptiles;
+  const int64_t nwg = w4_grid(batch, h, w, cout / (16 * CB), &ptiles);
   if (nwg >= (int64_t)1 << 31) return PD3_EUNSUPPORTED;
   conv3x3_winograd43_kernel<CB><<<(unsigned)nwg, 128 * CB, lds, s>>>(x, u_packed, bias, out, cin, cout, h, w, wv,
                                                                        relu, (int)ptiles);
@@ -312,14 +239,9 @@ static int launch_wino43(const float* x, const float* u_packed, const float* bia
 extern "C" int pd3_conv3x3_winograd43_bias_relu(const float* x, const float* u_packed, const float* bias,
                                                 int batch, int cin, int cout, int h, int w, int w_valid,
                                                 int relu, float* out, int channels_per_tile, void* stream) {
-  if (!x || !u_packed || !out || batch <= 0 || cin <= 0 || cout <= 0 || h <= 0 || w <= 0 || w_valid <= 0 ||
-      w_valid > w)
-    return PD3_EINVAL;
   if (channels_per_tile != 32 && channels_per_tile != 64) return PD3_EINVAL;
-  if (cin % kW4Ci != 0 || cout % channels_per_tile != 0 || w % 4 != 0) return PD3_EUNSUPPORTED;
-  if (reinterpret_cast<uintptr_t>(u_packed) % 16 != 0 || reinterpret_cast<uintptr_t>(x) % 16 != 0 ||
-      reinterpret_cast<uintptr_t>(out) % 16 != 0)
-    return PD3_EINVAL;
+  const int st = w4_check_args(x, u_packed, out, batch, cin, cout, h, w, w_valid, kW4Ci, channels_per_tile);
+  if (st != PD3_OK) return st;
   if ((int64_t)cin * h * w >= (int64_t)1 << 31) return PD3_EUNSUPPORTED;  // 32-bit staging offsets
   hipStream_t s = static_cast<hipStream_t>(stream);
   return channels_per_tile == 64 ? launch_wino43<4>(x, u_packed, bias, batch, cin, cout, h, w, w_valid, relu, out, s)

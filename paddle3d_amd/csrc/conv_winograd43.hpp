@@ -1,7 +1,12 @@
 // Shared pieces of the F(4x4, 3x3) kernels (conv_winograd43.hip: the packed form; conv_winograd43_pp.hip: the ping-pong
-// form of round 4): tile constants and the transform steps.
+// form of round 4; conv_winograd43_ppv.hip: the ping-pong form fed with a precomputed V): tile constants, the transform
+// steps, the MFMA stream, the output step, the tile decode and the entry points' common checks.  What only the two
+// ping-pong forms share is in conv_winograd43_pp.hpp.
 #pragma once
+#include "../../include/paddle3d_amd.h"
 #include "common.hpp"
+
+#include <type_traits>
 
 namespace pd3 {
 
@@ -50,5 +55,149 @@ __device__ __forceinline__ float w4_swap_pair(float v) {  // value of the neighb
 // barrier.  The kernels that use this wait for exactly the fetches a barrier has to publish (explicit s_waitcnt vmcnt(N))
 // and let the others travel across it (LDS-DMA requests stay in flight across s_barrier).
 __device__ __forceinline__ void w4_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// V = B^T d B of a thread pair's patch, from the six rows of this lane's three columns (rv[b][r] = d[r][3 hf + b]) to the
+// lane's 18 components at v.  Row pass on this lane's three columns, halves swapped between the pair, column pass on this
+// lane's three rows; components (row, nu) -> 6 row + nu.
+// (inline, not __forceinline__: forced in before its loops are unrolled, the SLP vectoriser pairs the passes differently --
+// 38 v_pk_fma_f32 where this gives 46 -- and the ping-pong kernel's register allocation moves with it; it is inlined in
+// both its callers either way)
+__device__ inline void w4_pair_transform(const float (&rv)[3][6], const int hf, float* v) {
+  float lo[3][3], hi[3][3];  // (B^T d)[row a or 3 + a][my column b]
+#pragma unroll
+  for (int b = 0; b < 3; ++b) {
+    float t[6];
+    w4_in(rv[b][0], rv[b][1], rv[b][2], rv[b][3], rv[b][4], rv[b][5], t);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      lo[a][b] = t[a];
+      hi[a][b] = t[3 + a];
+    }
+  }
+  // the even lane runs the column pass for rows 0..2, the odd lane for rows 3..5; what a lane lacks are the other three
+  // columns of its rows, i.e. the partner's lo (even lane) or hi (odd lane): one select with a DPP-swapped operand per
+  // value
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    float f[3], l[3];  // columns 0..2 / 3..5 of row 3 hf + a of B^T d
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+      const float ph = w4_swap_pair(hi[a][b]), pl = w4_swap_pair(lo[a][b]);
+      f[b] = hf ? ph : lo[a][b];
+      l[b] = hf ? hi[a][b] : pl;
+    }
+    float o[6];
+    w4_in(f[0], f[1], f[2], l[0], l[1], l[2], o);
+    *reinterpret_cast<w4_f32x2*>(v + a * 6 + 0) = (w4_f32x2){o[0], o[1]};
+    *reinterpret_cast<w4_f32x2*>(v + a * 6 + 2) = (w4_f32x2){o[2], o[3]};
+    *reinterpret_cast<w4_f32x2*>(v + a * 6 + 4) = (w4_f32x2){o[4], o[5]};
+  }
+}
+
+// N groups of 4 components (9 per trip of 4 input channels): b128 reads feed four MFMAs each; the reads run two groups
+// ahead of their MFMAs (ring of three).  B of group g is read from vptr(g).  A is either an array of N float4 already
+// in registers, or a functor g -> LDS address, read through a second ring.  hook() runs behind group HOOK's MFMAs (none
+// by default).
+struct w4_no_hook {
+  __device__ __forceinline__ void operator()() const {}
+};
+template <int N, int HOOK = -1, class UA, class VP, class F = w4_no_hook>
+__device__ __forceinline__ void w4_mfma_stream(w4_f32x4 (&acc)[36], const UA& ua, const VP& vptr, const F& hook = F()) {
+  constexpr bool kRing = !std::is_array<UA>::value;
+  w4_f32x4 a[3], b[3];
+  auto load = [&](const int g) {
+    if constexpr (kRing) a[g % 3] = *reinterpret_cast<const w4_f32x4*>(ua(g));
+    b[g % 3] = *reinterpret_cast<const w4_f32x4*>(vptr(g));
+  };
+  load(0);
+  load(1);
+#pragma unroll
+  for (int g = 0; g < N; ++g) {
+    if (g + 2 < N) load(g + 2);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float av;
+      if constexpr (kRing) av = a[g % 3][j];
+      else av = ua[g][j];
+      acc[(g % 9) * 4 + j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b[g % 3][j], acc[(g % 9) * 4 + j], 0, 0, 0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    if (g == HOOK) {
+      hook();
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+}
+
+// Output step: Y = A^T M A in registers, + bias, ReLU, zeros from column wv on, one non-temporal float4 store per output
+// row (16 lanes = 256 contiguous bytes).  The lane holds all 36 components of tile (oy, ox) for channels co0 + r (acc[c][r],
+// bias bv[r]).
+__device__ __forceinline__ void w4_output_step(const w4_f32x4 (&acc)[36], const w4_f32x4 bv, const int n, const int cout,
+                                               const int co0, const int oy, const int ox, const int h, const int w,
+                                               const int wv, const int relu, const int64_t plane,
+                                               float* __restrict__ out) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    float s[4][6];  // A^T M: column j of M through the row pass
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+      float c4[4];
+      w4_out(acc[0 * 6 + j][r], acc[1 * 6 + j][r], acc[2 * 6 + j][r], acc[3 * 6 + j][r], acc[4 * 6 + j][r],
+             acc[5 * 6 + j][r], c4);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) s[k][j] = c4[k];
+    }
+    float* o = out + ((int64_t)n * cout + co0 + r) * plane + (int64_t)oy * w + ox;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float y4[4];
+      w4_out(s[k][0], s[k][1], s[k][2], s[k][3], s[k][4], s[k][5], y4);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        y4[j] += bv[r];
+        if (relu) y4[j] = fmaxf(y4[j], 0.f);
+        if (ox + j >= wv) y4[j] = 0.f;
+      }
+      if (oy + k < h && ox < w)  // partial tiles at the border (w % 4 == 0: a quad is in or out)
+        __builtin_nontemporal_store((w4_f32x4){y4[0], y4[1], y4[2], y4[3]},
+                                    reinterpret_cast<w4_f32x4*>(o + (int64_t)k * w));
+    }
+  }
+}
+
+// XCD-aware tile order (see conv_winograd.hip): pixel tile pt lives on XCD pt % 8 with all its `groups` channel groups
+// (cg: this workgroup's).  A workgroup whose pt is not below the layer's pixel tiles has nothing to do.
+struct w4_tile {
+  int cg, pt, n, y0, x0;
+};
+__device__ __forceinline__ w4_tile w4_decode_block(const int groups, const int h, const int w) {
+  const int tiles_x = (w + 4 * kW4TC - 1) / (4 * kW4TC), tiles_y = (h + 4 * kW4TR - 1) / (4 * kW4TR);
+  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+  const int pt = (slot / groups) * 8 + xcd;
+  const int tx = pt % tiles_x, ty = (pt / tiles_x) % tiles_y;
+  return {slot % groups, pt, pt / (tiles_x * tiles_y), ty * 4 * kW4TR, tx * 4 * kW4TC};
+}
+
+// ---- host side -------------------------------------------------------------------------------------------------------------
+// What every entry point asks of (input, packed U, output) and of the layer's shape; the limits that differ (channel
+// multiples, 32-bit offsets) are the entry point's own.
+inline int w4_check_args(const void* in, const void* u, const void* out, int batch, int cin, int cout, int h, int w,
+                         int w_valid, int cin_multiple, int cout_multiple) {
+  if (!in || !u || !out || batch <= 0 || cin <= 0 || cout <= 0 || h <= 0 || w <= 0 || w_valid <= 0 || w_valid > w)
+    return PD3_EINVAL;
+  if (cin % cin_multiple != 0 || cout % cout_multiple != 0 || w % 4 != 0) return PD3_EUNSUPPORTED;
+  if (reinterpret_cast<uintptr_t>(in) % 16 != 0 || reinterpret_cast<uintptr_t>(u) % 16 != 0 ||
+      reinterpret_cast<uintptr_t>(out) % 16 != 0)
+    return PD3_EINVAL;
+  return PD3_OK;
+}
+
+// pixel tiles of a layer (-> *ptiles) and the workgroups of a launch that gives each of them `groups` channel groups: pixel
+// tiles rounded up to whole rounds of the 8 XCDs
+inline int64_t w4_grid(int batch, int h, int w, int groups, int64_t* ptiles) {
+  *ptiles = (int64_t)batch * ceil_div(h, 4 * kW4TR) * ceil_div(w, 4 * kW4TC);
+  return (*ptiles + 7) / 8 * 8 * groups;
+}
 
 }  // namespace pd3

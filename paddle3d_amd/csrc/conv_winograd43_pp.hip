@@ -3,7 +3,7 @@
 // bit) as conv_winograd43.hip (reference layers: second_backbone.py:72-120, center_head.py:43-220, cuDNN there).
 #include "../../include/paddle3d_amd.h"
 #include "common.hpp"
-#include "conv_winograd43.hpp"
+#include "conv_winograd43_pp.hpp"
 
 #include <type_traits>
 
@@ -49,15 +49,11 @@ namespace pd3 {
 // kernel already fills: 64 -> 64 at 256^2 317 -> 310 us with two items per workgroup, the other layers unchanged, four
 // items slower (too few workgroups).
 // ---------------------------------------------------------------------------------------------------------------------
-constexpr int kPpKT = 2;                                   // trips per slot
-constexpr int kPpCi = kPpKT * kW4Ci;                       // 8 input channels per slot
+// (the slot constants kPpKT .. kPpUsz: conv_winograd43_pp.hpp)
 constexpr int kPpRawR = 6;                                 // staged input rows of one tile row
 constexpr int kPpRawPl = kPpRawR * kW4RawW;                // 432 floats per channel
 constexpr int kPpRawSz = kPpCi * kPpRawPl;                 // 3456 floats per group
-constexpr int kPpVsz = kPpCi * kW4TC * kW4Cs;              // 4608 floats per group
 constexpr int kPpXPT = (2 * kPpRawPl / 4 + 63) / 64;       // 4 fetch pieces per wave: its two planes are 216 float4
-constexpr int kPpUHalf = 9 * 64 * 4;                       // 2304 floats: U of one trip for one wave (9 float4 per lane)
-constexpr int kPpUsz = kPpKT * 4 * kPpUHalf;               // 18432 floats per slot: [trip][cb][q][lane][4]
 
 __global__ __launch_bounds__(512, 1) void conv3x3_winograd43_pp_kernel(const float* __restrict__ x,
                                                                        const float* __restrict__ ulane,
@@ -74,13 +70,9 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winograd43_pp_kernel(const flo
   float* Us = smem;                                          // [2 trips][4 cb][9][64 lanes][4]: U of the current slot
   float* Raw = smem + kPpUsz + grp * (kPpRawSz + kPpVsz);    // [8 ci][6 rows][72 cols] of this group's tile row
   float* Vs = Raw + kPpRawSz;                      // [8 ci][16 tiles][36]
-  const int tiles_x = (w + 4 * kW4TC - 1) / (4 * kW4TC), tiles_y = (h + 4 * kW4TR - 1) / (4 * kW4TR);
-  const int nct = cout / CO;
-  const int xcd = blockIdx.x & 7, slot_id = blockIdx.x >> 3;
-  const int ct = slot_id % nct, pt = (slot_id / nct) * 8 + xcd;
-  if (pt >= ptiles) return;
-  const int tx = pt % tiles_x, ty = (pt / tiles_x) % tiles_y, n = pt / (tiles_x * tiles_y);
-  const int y0 = ty * 4 * kW4TR, x0 = tx * 4 * kW4TC;
+  const w4_tile tl = w4_decode_block(cout / CO, h, w);
+  if (tl.pt >= ptiles) return;
+  const int ct = tl.cg, n = tl.n, y0 = tl.y0, x0 = tl.x0;
   const int slots = cin / kPpCi;
   const int64_t plane = (int64_t)h * w;
   const float* xin = x + (int64_t)n * cin * plane;
@@ -105,9 +97,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winograd43_pp_kernel(const flo
   const int pci = pidx >> 4, ptile = pidx & 15;
   const int rsrc = pci * kPpRawPl + 4 * ptile + 3 + 3 * hf;
   const int vdst = (pci * kW4TC + ptile) * kW4Cs + 18 * hf;
-  // MFMA operands: B = V[(trip * 4 + k) ci][tile][component]; A = U of (co, ci) = (lane & 15, lane >> 4), float4 q of the
-  // lane's 36 components at Us[((trip * 4 + cb) * 9 + q) * 256 + 4 lane]
-  const int bbase = ((lane >> 4) * kW4TC + (lane & 15)) * kW4Cs;
+  const int bbase = pp_bbase(lane);
   const float* uct = ulane + (int64_t)ct * slots * kPpUsz;  // this workgroup's 64 output channels, all slots
 
   w4_f32x4 acc[36];
@@ -117,25 +107,15 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winograd43_pp_kernel(const flo
   // the wave's raw rows of slot s go from global memory straight into its planes of Raw (buffer_load_dwordx4 ... lds: no
   // staging registers, no store pass)
   auto fetch_x = [&](int s) {
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(xin + (int64_t)s * kPpCi * plane), 0, (int)(kPpCi * plane * 4), 0x00020000);
 #pragma unroll
     for (int i = 0; i < kPpXPT; ++i) {
       if (lane + i * 64 < kWvN4)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(
-            rs, (__attribute__((address_space(3))) void*)(Raw + 2 * cb * kPpRawPl + i * 256), 16, gofs[i], 0, 0, 0);
+        pp_dma(xin + (int64_t)s * kPpCi * plane, (unsigned)(kPpCi * plane * 4), Raw + 2 * cb * kPpRawPl + i * 256, gofs[i],
+               0);
     }
   };
-  // half hh of slot s of this wave's U block: 9 KB, contiguous in global memory and in LDS alike
-  const __amdgpu_buffer_rsrc_t urs =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(uct), 0, (int)((int64_t)slots * kPpUsz * 4), 0x00020000);
-  auto fetch_u = [&](int s, int hh) {
-    const int blk = (hh * 4 + cb) * kPpUHalf;
-#pragma unroll
-    for (int q = 0; q < 9; ++q)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(urs, (__attribute__((address_space(3))) void*)(Us + blk + q * 256), 16,
-                                               lane * 16, (s * kPpUsz + blk + q * 256) * 4, 0, 0);
-  };
+  // half hh of slot s of this wave's U block
+  auto fetch_u = [&](int s, int hh) { pp_fetch_u(uct, (unsigned)((int64_t)slots * kPpUsz * 4), Us, cb, lane, s, hh); };
   // The wave's raw rows of the NEXT transform slot are read into registers at the end of the wave's multiply slot, in front
   // of the barrier: behind it the other group's MFMAs hold the SIMD, and LDS reads issued then return when that stream
   // ends (pingpong_skeleton: more than four reads wait for it) -- 340-450 cycles of every time slot.
@@ -148,7 +128,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winograd43_pp_kernel(const flo
       for (int r = 0; r < 6; ++r) rv[b][r] = d[r * kW4RawW];
     }
   };
-  // V = B^T d B of this thread pair's patch (as W4_TRANSFORM above), from the rows in rv[].  The fetch of the NEXT slot's
+  // V = B^T d B of this thread pair's patch (w4_pair_transform), from the rows in rv[].  The fetch of the NEXT slot's
   // rows (slot sn) goes out first -- the memory pipe takes it while the SIMD is held -- and has the rest of this slot and
   // the wave's multiply slot to land.
   auto transform = [&](int sn, auto&& after_fetch) {
@@ -156,33 +136,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winograd43_pp_kernel(const flo
     after_fetch();
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_sched_barrier(0);
-    float lo[3][3], hi[3][3];
-#pragma unroll
-    for (int b = 0; b < 3; ++b) {
-      float t[6];
-      w4_in(rv[b][0], rv[b][1], rv[b][2], rv[b][3], rv[b][4], rv[b][5], t);
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        lo[a][b] = t[a];
-        hi[a][b] = t[3 + a];
-      }
-    }
-    float* v = Vs + vdst;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      float f[3], l[3];
-#pragma unroll
-      for (int b = 0; b < 3; ++b) {
-        const float ph = w4_swap_pair(hi[a][b]), pl = w4_swap_pair(lo[a][b]);
-        f[b] = hf ? ph : lo[a][b];
-        l[b] = hf ? hi[a][b] : pl;
-      }
-      float o[6];
-      w4_in(f[0], f[1], f[2], l[0], l[1], l[2], o);
-      *reinterpret_cast<w4_f32x2*>(v + a * 6 + 0) = (w4_f32x2){o[0], o[1]};
-      *reinterpret_cast<w4_f32x2*>(v + a * 6 + 2) = (w4_f32x2){o[2], o[3]};
-      *reinterpret_cast<w4_f32x2*>(v + a * 6 + 4) = (w4_f32x2){o[4], o[5]};
-    }
+    w4_pair_transform(rv, hf, Vs + vdst);
   };
   // a multiply slot: 72 MFMAs, one stream over both trips, fed by ds_read_b128 alone; B through a ring of three reads, two
   // groups ahead.  No buffer_load ... lds here: one piece costs an MFMA stream 60-185 cycles of issue (measured: a group
@@ -190,60 +144,17 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winograd43_pp_kernel(const flo
   //   group 0: A through a second ring, straight from Us (whose refill landed before the barrier in front of this slot);
   //   group 1: A from the registers ua[], read from Us at the end of its transform slot -- the SAME time slot in which
   //            group 0 reads, so that Us is free for the refill one slot later.
-  auto vptr = [&](int g) { return Vs + (g / 9) * (kW4Ci * kW4TC * kW4Cs) + bbase + (g % 9) * 4; };
-  auto uptr = [&](int g) { return Us + (((g / 9) * 4 + cb) * 9 + (g % 9)) * 256 + lane * 4; };
+  auto vptr = [&](int g) { return pp_vptr(Vs, bbase, g); };
+  auto uptr = [&](int g) { return pp_uptr(Us, cb, lane, g); };
   w4_f32x4 ua[18];
-  auto multiply_ring = [&]() {
-    w4_f32x4 a[3], b[3];
-    a[0] = *reinterpret_cast<const w4_f32x4*>(uptr(0));
-    b[0] = *reinterpret_cast<const w4_f32x4*>(vptr(0));
-    a[1] = *reinterpret_cast<const w4_f32x4*>(uptr(1));
-    b[1] = *reinterpret_cast<const w4_f32x4*>(vptr(1));
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-#pragma unroll
-      for (int g9 = 0; g9 < 9; ++g9) {
-        const int g = t * 9 + g9;
-        if (g + 2 < 18) {
-          a[(g + 2) % 3] = *reinterpret_cast<const w4_f32x4*>(uptr(g + 2));
-          b[(g + 2) % 3] = *reinterpret_cast<const w4_f32x4*>(vptr(g + 2));
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc[g9 * 4 + j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[g % 3][j], b[g % 3][j], acc[g9 * 4 + j], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        if (g == 15) {  // the rows of the wave's next transform slot (fetched a slot ago), behind the last ring reads
-          __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0)
-          read_rows();
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-    }
+  // the rows of the wave's next transform slot (fetched a slot ago) go behind the last ring reads: behind group 15 of the
+  // ring form; one group later with A in registers: by then all but four of the 72 registers of ua[] are free
+  auto next_rows = [&]() {
+    __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0)
+    read_rows();
   };
-  auto multiply_regs = [&]() {
-    w4_f32x4 b[3];
-    b[0] = *reinterpret_cast<const w4_f32x4*>(vptr(0));
-    b[1] = *reinterpret_cast<const w4_f32x4*>(vptr(1));
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-#pragma unroll
-      for (int g9 = 0; g9 < 9; ++g9) {
-        const int g = t * 9 + g9;
-        if (g + 2 < 18) b[(g + 2) % 3] = *reinterpret_cast<const w4_f32x4*>(vptr(g + 2));
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc[g9 * 4 + j] = __builtin_amdgcn_mfma_f32_16x16x4f32(ua[g][j], b[g % 3][j], acc[g9 * 4 + j], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        if (g == 16) {  // as above, one group later: by then all but four of the 72 registers of ua[] are free
-          __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0)
-          read_rows();
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-    }
-  };
+  auto multiply_ring = [&]() { w4_mfma_stream<18, 15>(acc, uptr, vptr, next_rows); };
+  auto multiply_regs = [&]() { w4_mfma_stream<18, 16>(acc, ua, vptr, next_rows); };
 
   // prologue: the raw rows of slot 0 (each wave its own) and slot 0's U (group 0's waves, as in the loop)
   fetch_x(0);
@@ -313,43 +224,14 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winograd43_pp_kernel(const flo
     dbg[wave * 4 + 3] = (clock64() - t_all) | ((long long)__builtin_amdgcn_s_getreg(2308) << 56);  // + SIMD id (HW_ID[5:4])
   }
 
-  // epilogue (as above): Y = A^T M A; lane: tile column lane & 15, channels 4 (lane >> 4) + r of the co block
-  float bv[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) bv[r] = 0.f;
+  // epilogue: lane: tile column lane & 15, channels 4 (lane >> 4) + r of the co block
+  w4_f32x4 bv = {0.f, 0.f, 0.f, 0.f};
   const int co0 = ct * CO + cb * 16 + 4 * (lane >> 4);
   if (bias) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) bv[r] = bias[co0 + r];
   }
-  const int oy = y0 + 4 * grp, ox = x0 + 4 * (lane & 15);
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    float sm[4][6];
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-      float c4[4];
-      w4_out(acc[0 * 6 + j][r], acc[1 * 6 + j][r], acc[2 * 6 + j][r], acc[3 * 6 + j][r], acc[4 * 6 + j][r],
-             acc[5 * 6 + j][r], c4);
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) sm[kk][j] = c4[kk];
-    }
-    float* o = out + ((int64_t)n * cout + co0 + r) * plane + (int64_t)oy * w + ox;
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-      float y4[4];
-      w4_out(sm[kk][0], sm[kk][1], sm[kk][2], sm[kk][3], sm[kk][4], sm[kk][5], y4);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        y4[j] += bv[r];
-        if (relu) y4[j] = fmaxf(y4[j], 0.f);
-        if (ox + j >= wv) y4[j] = 0.f;
-      }
-      if (oy + kk < h && ox < w)
-        __builtin_nontemporal_store((w4_f32x4){y4[0], y4[1], y4[2], y4[3]},
-                                    reinterpret_cast<w4_f32x4*>(o + (int64_t)kk * w));
-    }
-  }
+  w4_output_step(acc, bv, n, cout, co0, y0 + 4 * grp, x0 + 4 * (lane & 15), h, w, wv, relu, plane, out);
 }
 
 }  // namespace pd3
@@ -362,8 +244,8 @@ static int launch_wino43_pp(const float* x, const float* u_lane, const float* bi
   const void* fn = reinterpret_cast<const void*>(conv3x3_winograd43_pp_kernel);
   hipError_t e = pd3_max_dynamic_lds(fn, (int)lds);
   if (e != hipSuccess) return (int)e;
-  const int64_t ptiles = (int64_t)batch * ceil_div(h, 4 * kW4TR) * ceil_div(w, 4 * kW4TC);
-  const int64_t nwg = (ptiles + 7) / 8 * 8 * (cout / 64);
+  int64_t ptiles;
+  const int64_t nwg = w4_grid(batch, h, w, cout / 64, &ptiles);
   if (nwg >= (int64_t)1 << 31) return PD3_EUNSUPPORTED;
   conv3x3_winograd43_pp_kernel<<<(unsigned)nwg, 512, lds, s>>>(x, u_lane, bias, out, cin, cout, h, w, w_valid, relu,
                                                                (int)ptiles, dbg);
@@ -372,12 +254,8 @@ static int launch_wino43_pp(const float* x, const float* u_lane, const float* bi
 
 static int check_wino43_pp(const float* x, const float* u_lane, const float* out, int batch, int cin, int cout, int h,
                            int w, int w_valid) {
-  if (!x || !u_lane || !out || batch <= 0 || cin <= 0 || cout <= 0 || h <= 0 || w <= 0 || w_valid <= 0 || w_valid > w)
-    return PD3_EINVAL;
-  if (cin % kPpCi != 0 || cout % 64 != 0 || w % 4 != 0) return PD3_EUNSUPPORTED;
-  if (reinterpret_cast<uintptr_t>(x) % 16 != 0 || reinterpret_cast<uintptr_t>(out) % 16 != 0 ||
-      reinterpret_cast<uintptr_t>(u_lane) % 16 != 0)
-    return PD3_EINVAL;
+  const int st = w4_check_args(x, u_lane, out, batch, cin, cout, h, w, w_valid, kPpCi, 64);
+  if (st != PD3_OK) return st;
   if ((int64_t)kPpCi * h * w >= (int64_t)1 << 29) return PD3_EUNSUPPORTED;       // 32-bit byte offsets inside a slot
   if ((int64_t)(cin / kPpCi) * kPpUsz >= (int64_t)1 << 29) return PD3_EUNSUPPORTED;  // and inside a channel tile's U
   return PD3_OK;

@@ -12,17 +12,13 @@
 // the same bytes out as conv_winograd43_pp.hip (tested).
 #include "../../include/paddle3d_amd.h"
 #include "common.hpp"
-#include "conv_winograd43.hpp"
+#include "conv_winograd43_pp.hpp"
 
 #include <type_traits>
 
 namespace pd3 {
 
-constexpr int kPvKT = 2;                                   // trips per slot
-constexpr int kPvCi = kPvKT * kW4Ci;                       // 8 input channels per slot
-constexpr int kPvVsz = kPvCi * kW4TC * kW4Cs;              // 4608 floats per (tile row, slot): [8 ci][16 tiles][36]
-constexpr int kPvUHalf = 9 * 64 * 4;                       // 2304 floats: U of one trip for one wave
-constexpr int kPvUsz = kPvKT * 4 * kPvUHalf;               // 18432 floats per slot
+// (the slot constants kPpCi, kPpVsz, kPpUsz: conv_winograd43_pp.hpp)
 constexpr int kPvMaxBlocks = 18;                           // channel blocks a workgroup walks at most (their bias sits in LDS)
 
 // V[pixel tile pt][slot s][tile row g][ci 8][tile 16][36]: one workgroup = one (pt, s, g) block of 18 432 bytes; thread =
@@ -32,12 +28,12 @@ constexpr int kPvMaxBlocks = 18;                           // channel blocks a w
 __global__ __launch_bounds__(128) void w43_input_transform_kernel(const float* __restrict__ x, int cin, int h, int w,
                                                                   int wv, int tiles_x, int tiles_y, int slots,
                                                                   float* __restrict__ v) {
-  __shared__ __attribute__((aligned(16))) float blk[kPvVsz];
+  __shared__ __attribute__((aligned(16))) float blk[kPpVsz];
   const int g = blockIdx.x & 1, s = (blockIdx.x >> 1) % slots, pt = (blockIdx.x >> 1) / slots;
   const int tx = pt % tiles_x, ty = (pt / tiles_x) % tiles_y, n = pt / (tiles_x * tiles_y);
   const int ci = threadIdx.x >> 4, tile = threadIdx.x & 15;
   const int y0 = ty * 4 * kW4TR + 4 * g - 1, x0 = tx * 4 * kW4TC + 4 * tile - 1;
-  const float* xin = x + ((int64_t)n * cin + s * kPvCi + ci) * (int64_t)h * w;
+  const float* xin = x + ((int64_t)n * cin + s * kPpCi + ci) * (int64_t)h * w;
   float d[6][6];
 #pragma unroll
   for (int r = 0; r < 6; ++r)
@@ -63,16 +59,10 @@ __global__ __launch_bounds__(128) void w43_input_transform_kernel(const float* _
     for (int c = 0; c < 6; ++c) dst[a * 6 + c] = o[c];
   }
   __syncthreads();
-  w4_f32x4* out4 = reinterpret_cast<w4_f32x4*>(v + (int64_t)blockIdx.x * kPvVsz);  // block index = (pt * slots + s) * 2 + g
+  w4_f32x4* out4 = reinterpret_cast<w4_f32x4*>(v + (int64_t)blockIdx.x * kPpVsz);  // block index = (pt * slots + s) * 2 + g
   const w4_f32x4* b4 = reinterpret_cast<const w4_f32x4*>(blk);
 #pragma unroll
-  for (int i = 0; i < kPvVsz / 4 / 128; ++i) out4[threadIdx.x + i * 128] = b4[threadIdx.x + i * 128];
-}
-
-// 64 lanes x 16 bytes from base + voff + soff to lds .. lds + 1023
-__device__ __forceinline__ void pv_dma(const float* base, unsigned bytes, float* lds, unsigned voff, unsigned soff) {
-  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, (int)bytes, 0x00020000);
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds, 16, (int)voff, (int)soff, 0, 0);
+  for (int i = 0; i < kPpVsz / 4 / 128; ++i) out4[threadIdx.x + i * 128] = b4[threadIdx.x + i * 128];
 }
 
 __global__ __launch_bounds__(512, 1) void conv3x3_winograd43_ppv_kernel(const float* __restrict__ vpre,
@@ -85,26 +75,22 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winograd43_ppv_kernel(const fl
   const int lane = lane_id(), wave = __builtin_amdgcn_readfirstlane(wave_id());
   const int grp = wave >> 2, cb = wave & 3;  // tile row / 16-channel block of this wave; waves w and w + 4 share a SIMD
   float* Us = smem;                                  // [2 trips][4 cb][9][64 lanes][4]: U of the current slot
-  float* Vs = smem + kPvUsz + grp * 2 * kPvVsz;      // [2 buffers][8 ci][16 tiles][36] of this group's tile row
-  float* bias_s = smem + kPvUsz + 4 * kPvVsz;        // [ipw][64]: the bias of this workgroup's channel blocks
-  const int tiles_x = (w + 4 * kW4TC - 1) / (4 * kW4TC), tiles_y = (h + 4 * kW4TR - 1) / (4 * kW4TR);
+  float* Vs = smem + kPpUsz + grp * 2 * kPpVsz;      // [2 buffers][8 ci][16 tiles][36] of this group's tile row
+  float* bias_s = smem + kPpUsz + 4 * kPpVsz;        // [ipw][64]: the bias of this workgroup's channel blocks
   // a workgroup walks `ipw` consecutive channel blocks of ONE pixel tile (they read the same V): the first fetches of block
   // i + 1 travel under the output transform of block i, whose stores drain under block i + 1's first slots (cycle stamps of
   // the one-block form, the head's 64 -> 1152 slice: prologue 5.9 k, eight slot pairs 41.7 k, epilogue 7-9 k cycles)
-  const int ncg = (cout / CO) / ipw;
-  const int xcd = blockIdx.x & 7, slot_id = blockIdx.x >> 3;
-  const int ct0 = (slot_id % ncg) * ipw, pt = (slot_id / ncg) * 8 + xcd;
-  if (pt >= ptiles) return;
-  const int tx = pt % tiles_x, ty = (pt / tiles_x) % tiles_y, n = pt / (tiles_x * tiles_y);
-  const int y0 = ty * 4 * kW4TR, x0 = tx * 4 * kW4TC;
-  const int slots = cin / kPvCi;
+  const w4_tile tl = w4_decode_block((cout / CO) / ipw, h, w);
+  if (tl.pt >= ptiles) return;
+  const int ct0 = tl.cg * ipw, pt = tl.pt, n = tl.n, y0 = tl.y0, x0 = tl.x0;
+  const int slots = cin / kPpCi;
   const bool whole_tiles = h % (4 * kW4TR) == 0 && w % (4 * kW4TC) == 0;
   const int64_t plane = (int64_t)h * w;
-  const int bbase = ((lane >> 4) * kW4TC + (lane & 15)) * kW4Cs;
+  const int bbase = pp_bbase(lane);
   // this pixel tile's V: [slot][tile row][4608]; the group's block of slot s = 18 fetches of 1 KB, wave cb sends pieces
   // cb, cb + 4, .. (five for cb < 2, four otherwise)
-  const float* vpt = vpre + (int64_t)pt * slots * 2 * kPvVsz;
-  const unsigned vbytes = (unsigned)(slots * 2 * kPvVsz * 4);
+  const float* vpt = vpre + (int64_t)pt * slots * 2 * kPpVsz;
+  const unsigned vbytes = (unsigned)(slots * 2 * kPpVsz * 4);
   const int nv = cb < 2 ? 5 : 4;
 
   w4_f32x4 acc[36];
@@ -112,69 +98,25 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winograd43_ppv_kernel(const fl
   for (int c = 0; c < 36; ++c) acc[c] = (w4_f32x4){0.f, 0.f, 0.f, 0.f};
 
   auto fetch_v = [&](int s) {
-    float* dst = Vs + (s & 1) * kPvVsz;
-    const unsigned so = (unsigned)((s * 2 + grp) * kPvVsz * 4);
+    float* dst = Vs + (s & 1) * kPpVsz;
+    const unsigned so = (unsigned)((s * 2 + grp) * kPpVsz * 4);
 #pragma unroll
     for (int i = 0; i < 5; ++i) {
       const int piece = cb + 4 * i;
-      if (i < 4 || cb < 2) pv_dma(vpt, vbytes, dst + piece * 256, lane * 16, so + piece * 1024);
+      if (i < 4 || cb < 2) pp_dma(vpt, vbytes, dst + piece * 256, lane * 16, so + piece * 1024);
     }
   };
-  const unsigned ubytes = (unsigned)((int64_t)(cout / CO) * slots * kPvUsz * 4);
+  const unsigned ubytes = (unsigned)((int64_t)(cout / CO) * slots * kPpUsz * 4);
   int ct = ct0;  // the channel block being multiplied
   auto fetch_u = [&](int c, int s, int hh) {  // half hh of slot s of channel block c
-    const int blk = (hh * 4 + cb) * kPvUHalf;
-    const unsigned so = __builtin_amdgcn_readfirstlane((unsigned)(((c * slots + s) * kPvUsz + blk) * 4));
-#pragma unroll
-    for (int q = 0; q < 9; ++q) pv_dma(ulane, ubytes, Us + blk + q * 256, lane * 16, so + (unsigned)(q * 1024));
+    pp_fetch_u(ulane, ubytes, Us, cb, lane, c * slots + s, hh);
   };
   // a multiply slot: 72 MFMAs, one stream over both trips, fed by ds_read_b128 alone (as conv_winograd43_pp.hip; no fetch
   // is waited for inside it)
-  auto multiply_ring = [&](const float* V) {
-    auto vptr = [&](int g) { return V + (g / 9) * (kW4Ci * kW4TC * kW4Cs) + bbase + (g % 9) * 4; };
-    auto uptr = [&](int g) { return Us + (((g / 9) * 4 + cb) * 9 + (g % 9)) * 256 + lane * 4; };
-    w4_f32x4 a[3], b[3];
-    a[0] = *reinterpret_cast<const w4_f32x4*>(uptr(0));
-    b[0] = *reinterpret_cast<const w4_f32x4*>(vptr(0));
-    a[1] = *reinterpret_cast<const w4_f32x4*>(uptr(1));
-    b[1] = *reinterpret_cast<const w4_f32x4*>(vptr(1));
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-#pragma unroll
-      for (int g9 = 0; g9 < 9; ++g9) {
-        const int g = t * 9 + g9;
-        if (g + 2 < 18) {
-          a[(g + 2) % 3] = *reinterpret_cast<const w4_f32x4*>(uptr(g + 2));
-          b[(g + 2) % 3] = *reinterpret_cast<const w4_f32x4*>(vptr(g + 2));
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc[g9 * 4 + j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[g % 3][j], b[g % 3][j], acc[g9 * 4 + j], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-  };
+  auto uptr = [&](int g) { return pp_uptr(Us, cb, lane, g); };
   w4_f32x4 ua[18];
-  auto multiply_regs = [&](const float* V) {
-    auto vptr = [&](int g) { return V + (g / 9) * (kW4Ci * kW4TC * kW4Cs) + bbase + (g % 9) * 4; };
-    w4_f32x4 b[3];
-    b[0] = *reinterpret_cast<const w4_f32x4*>(vptr(0));
-    b[1] = *reinterpret_cast<const w4_f32x4*>(vptr(1));
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-#pragma unroll
-      for (int g9 = 0; g9 < 9; ++g9) {
-        const int g = t * 9 + g9;
-        if (g + 2 < 18) b[(g + 2) % 3] = *reinterpret_cast<const w4_f32x4*>(vptr(g + 2));
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc[g9 * 4 + j] = __builtin_amdgcn_mfma_f32_16x16x4f32(ua[g][j], b[g % 3][j], acc[g9 * 4 + j], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-  };
+  auto multiply_ring = [&](const float* V) { w4_mfma_stream<18>(acc, uptr, [&](int g) { return pp_vptr(V, bbase, g); }); };
+  auto multiply_regs = [&](const float* V) { w4_mfma_stream<18>(acc, ua, [&](int g) { return pp_vptr(V, bbase, g); }); };
 
   // prologue: the bias of the workgroup's blocks, V of slot 0 (each group its own tile row) and slot 0's U (group 0's waves)
   for (int t = threadIdx.x; t < ipw * CO; t += 512) bias_s[t] = bias ? bias[ct0 * CO + t] : 0.f;
@@ -202,7 +144,6 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winograd43_ppv_kernel(const fl
         const bool more = s + 1 < slots;
         if (more) fetch_v(s + 1);
         if (!G0) {
-          auto uptr = [&](int g) { return Us + (((g / 9) * 4 + cb) * 9 + (g % 9)) * 256 + lane * 4; };
 #pragma unroll
           for (int g = 0; g < 18; ++g) ua[g] = *reinterpret_cast<const w4_f32x4*>(uptr(g));
         }
@@ -219,7 +160,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winograd43_ppv_kernel(const fl
       }
       w4_lds_barrier();
       {  // multiply slot s
-        const float* V = Vs + (s & 1) * kPvVsz;
+        const float* V = Vs + (s & 1) * kPpVsz;
         if (G0) multiply_ring(V);
         else multiply_regs(V);
       }
@@ -242,42 +183,10 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winograd43_ppv_kernel(const fl
     }
   }
 
-  // epilogue (as conv_winograd43_pp.hip): Y = A^T M A; lane: tile column lane & 15, channels 4 (lane >> 4) + r of the block
-  float bv[4];
+  // epilogue (as conv_winograd43_pp.hip): lane: tile column lane & 15, channels 4 (lane >> 4) + r of the block
   const int co0 = ct * CO + cb * 16 + 4 * (lane >> 4);
-  {
-    const w4_f32x4 b4 = *reinterpret_cast<const w4_f32x4*>(bias_s + it * CO + cb * 16 + 4 * (lane >> 4));
-#pragma unroll
-    for (int r = 0; r < 4; ++r) bv[r] = b4[r];
-  }
-  const int oy = y0 + 4 * grp, ox = x0 + 4 * (lane & 15);
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    float sm[4][6];
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-      float c4[4];
-      w4_out(acc[0 * 6 + j][r], acc[1 * 6 + j][r], acc[2 * 6 + j][r], acc[3 * 6 + j][r], acc[4 * 6 + j][r],
-             acc[5 * 6 + j][r], c4);
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) sm[kk][j] = c4[kk];
-    }
-    float* o = out + ((int64_t)n * cout + co0 + r) * plane + (int64_t)oy * w + ox;
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-      float y4[4];
-      w4_out(sm[kk][0], sm[kk][1], sm[kk][2], sm[kk][3], sm[kk][4], sm[kk][5], y4);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        y4[j] += bv[r];
-        if (relu) y4[j] = fmaxf(y4[j], 0.f);
-        if (ox + j >= wv) y4[j] = 0.f;
-      }
-      if (oy + kk < h && ox < w)
-        __builtin_nontemporal_store((w4_f32x4){y4[0], y4[1], y4[2], y4[3]},
-                                    reinterpret_cast<w4_f32x4*>(o + (int64_t)kk * w));
-    }
-  }
+  const w4_f32x4 b4 = *reinterpret_cast<const w4_f32x4*>(bias_s + it * CO + cb * 16 + 4 * (lane >> 4));
+  w4_output_step(acc, b4, n, cout, co0, y0 + 4 * grp, x0 + 4 * (lane & 15), h, w, wv, relu, plane, out);
   if (it + 1 < ipw) {
 #pragma unroll
     for (int c = 0; c < 36; ++c) acc[c] = (w4_f32x4){0.f, 0.f, 0.f, 0.f};
@@ -299,49 +208,46 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winograd43_ppv_kernel(const fl
 using namespace pd3;
 
 extern "C" size_t pd3_winograd43_input_transform_floats(int batch, int cin, int h, int w) {
-  if (batch <= 0 || cin <= 0 || h <= 0 || w <= 0 || cin % kPvCi != 0) return 0;
-  const int64_t ptiles = (int64_t)batch * ceil_div(h, 4 * kW4TR) * ceil_div(w, 4 * kW4TC);
-  return (size_t)(ptiles * (cin / kPvCi) * 2 * kPvVsz);
+  if (batch <= 0 || cin <= 0 || h <= 0 || w <= 0 || cin % kPpCi != 0) return 0;
+  int64_t ptiles;
+  w4_grid(batch, h, w, 1, &ptiles);
+  return (size_t)(ptiles * (cin / kPpCi) * 2 * kPpVsz);
 }
 
 extern "C" int pd3_winograd43_input_transform(const float* x, int batch, int cin, int h, int w, int w_valid, float* v,
                                               void* stream) {
   if (!x || !v || batch <= 0 || cin <= 0 || h <= 0 || w <= 0 || w_valid <= 0 || w_valid > w) return PD3_EINVAL;
-  if (cin % kPvCi != 0) return PD3_EUNSUPPORTED;
+  if (cin % kPpCi != 0) return PD3_EUNSUPPORTED;
   if (reinterpret_cast<uintptr_t>(v) % 16 != 0) return PD3_EINVAL;
   const int tiles_x = (int)ceil_div(w, 4 * kW4TC), tiles_y = (int)ceil_div(h, 4 * kW4TR);
-  const int64_t blocks = (int64_t)batch * tiles_x * tiles_y * (cin / kPvCi) * 2;
+  const int64_t blocks = (int64_t)batch * tiles_x * tiles_y * (cin / kPpCi) * 2;
   if (blocks >= (int64_t)1 << 31) return PD3_EUNSUPPORTED;
   w43_input_transform_kernel<<<(unsigned)blocks, 128, 0, static_cast<hipStream_t>(stream)>>>(x, cin, h, w, w_valid, tiles_x,
-                                                                                           tiles_y, cin / kPvCi, v);
+                                                                                           tiles_y, cin / kPpCi, v);
   return launch_status();
 }
 
 extern "C" int pd3_conv3x3_winograd43_ppv_bias_relu(const float* v_pre, const float* u_lane, const float* bias, int batch,
                                                     int cin, int cout, int h, int w, int w_valid, int relu, float* out,
                                                     void* stream) {
-  if (!v_pre || !u_lane || !out || batch <= 0 || cin <= 0 || cout <= 0 || h <= 0 || w <= 0 || w_valid <= 0 || w_valid > w)
-    return PD3_EINVAL;
-  if (cin % kPvCi != 0 || cout % 64 != 0 || w % 4 != 0) return PD3_EUNSUPPORTED;
-  if (reinterpret_cast<uintptr_t>(v_pre) % 16 != 0 || reinterpret_cast<uintptr_t>(out) % 16 != 0 ||
-      reinterpret_cast<uintptr_t>(u_lane) % 16 != 0)
-    return PD3_EINVAL;
-  if ((int64_t)(cout / 64) * (cin / kPvCi) * kPvUsz >= (int64_t)1 << 29 ||
-      (int64_t)(cin / kPvCi) * 2 * kPvVsz >= (int64_t)1 << 29)
+  const int st = w4_check_args(v_pre, u_lane, out, batch, cin, cout, h, w, w_valid, kPpCi, 64);
+  if (st != PD3_OK) return st;
+  if ((int64_t)(cout / 64) * (cin / kPpCi) * kPpUsz >= (int64_t)1 << 29 ||
+      (int64_t)(cin / kPpCi) * 2 * kPpVsz >= (int64_t)1 << 29)
     return PD3_EUNSUPPORTED;  // 32-bit byte offsets inside U and inside a pixel tile's V
   // channel blocks per workgroup: the largest divisor of cout / 64 (up to kPvMaxBlocks) that still leaves six workgroups per
   // CU (the head's 18 blocks per slice, 16 frames: 3 / 6 / 9 / 18 blocks per workgroup = 831 / 812 / 830 / 849 us)
   const int nct = cout / 64;
-  const int64_t ptiles8 = (((int64_t)batch * ceil_div(h, 4 * kW4TR) * ceil_div(w, 4 * kW4TC)) + 7) / 8 * 8;
+  int64_t ptiles;
+  const int64_t ptiles8 = w4_grid(batch, h, w, 1, &ptiles);
   int ipw = 1;
   for (int d = 2; d <= kPvMaxBlocks; ++d)
     if (nct % d == 0 && ptiles8 * (nct / d) >= 6 * 256) ipw = d;
-  const size_t lds = ((size_t)kPvUsz + 4 * kPvVsz + kPvMaxBlocks * 64) * sizeof(float);  // 147 456 B + the blocks' bias
+  const size_t lds = ((size_t)kPpUsz + 4 * kPpVsz + kPvMaxBlocks * 64) * sizeof(float);  // 147 456 B + the blocks' bias
   const void* fn = reinterpret_cast<const void*>(conv3x3_winograd43_ppv_kernel);
   const hipError_t e = pd3_max_dynamic_lds(fn, (int)lds);
   if (e != hipSuccess) return (int)e;
-  const int64_t ptiles = (int64_t)batch * ceil_div(h, 4 * kW4TR) * ceil_div(w, 4 * kW4TC);
-  const int64_t nwg = (ptiles + 7) / 8 * 8 * (nct / ipw);
+  const int64_t nwg = ptiles8 * (nct / ipw);
   if (nwg >= (int64_t)1 << 31) return PD3_EUNSUPPORTED;
   conv3x3_winograd43_ppv_kernel<<<(unsigned)nwg, 512, lds, static_cast<hipStream_t>(stream)>>>(
       v_pre, u_lane, bias, out, cin, cout, h, w, w_valid, relu, (int)ptiles, ipw);

@@ -155,16 +155,20 @@ def winograd43_tile(cout: int) -> int:
     return 64 if cout % 64 == 0 else 32
 
 
+def _winograd43_u(weight: torch.Tensor) -> torch.Tensor:
+    """[Cout, Cin, 3, 3] -> U = G g G^T (6x6, F(4x4,3x3)) [Cout, Cin, 6, 6], computed in fp64 and rounded once."""
+    g = torch.tensor([[1 / 4, 0, 0], [-1 / 6, -1 / 6, -1 / 6], [-1 / 6, 1 / 6, -1 / 6], [1 / 24, 1 / 12, 1 / 6],
+                      [1 / 24, -1 / 12, 1 / 6], [0, 0, 1]], dtype=torch.float64, device=weight.device)
+    return torch.einsum("ij,ocjk,lk->ocil", g, weight.double(), g).float()
+
+
 def pack_winograd43_weight(weight: torch.Tensor, tile: int | None = None) -> torch.Tensor:
     """[Cout, Cin, 3, 3] -> U = G g G^T (6x6, F(4x4,3x3)) packed [Cout/T][Cin/4][T/16 blocks][4 ci][16 co][36],
     T = channels per workgroup (winograd43_tile(Cout) by default)."""
     cout, cin = weight.shape[:2]
     t = winograd43_tile(cout) if tile is None else tile
     assert weight.shape[2:] == (3, 3) and cout % t == 0 and cin % 4 == 0 and t in (32, 64)
-    g = torch.tensor([[1 / 4, 0, 0], [-1 / 6, -1 / 6, -1 / 6], [-1 / 6, 1 / 6, -1 / 6], [1 / 24, 1 / 12, 1 / 6],
-                      [1 / 24, -1 / 12, 1 / 6], [0, 0, 1]], dtype=torch.float64, device=weight.device)
-    u = torch.einsum("ij,ocjk,lk->ocil", g, weight.double(), g).float()  # [cout, cin, 6, 6]
-    u = u.reshape(cout // t, t // 16, 16, cin // 4, 4, 36).permute(0, 3, 1, 4, 2, 5)
+    u = _winograd43_u(weight).reshape(cout // t, t // 16, 16, cin // 4, 4, 36).permute(0, 3, 1, 4, 2, 5)
     return u.contiguous()
 
 
@@ -566,11 +570,8 @@ def pack_winograd43_lane_weight(weight: torch.Tensor) -> torch.Tensor:
     [Cout/64][Cin/8][2 trips][4 blocks][9][64 lanes][4], lane = 16 (ci % 4) + (co % 16)."""
     cout, cin = weight.shape[:2]
     assert weight.shape[2:] == (3, 3) and cout % 64 == 0 and cin % 8 == 0
-    g = torch.tensor([[1 / 4, 0, 0], [-1 / 6, -1 / 6, -1 / 6], [-1 / 6, 1 / 6, -1 / 6], [1 / 24, 1 / 12, 1 / 6],
-                      [1 / 24, -1 / 12, 1 / 6], [0, 0, 1]], dtype=torch.float64, device=weight.device)
-    u = torch.einsum("ij,ocjk,lk->ocil", g, weight.double(), g).float()  # [cout, cin, 6, 6]
     #          ct          cb 16co  slot      trip ci4 q  j
-    u = u.reshape(cout // 64, 4, 16, cin // 8, 2, 4, 9, 4).permute(0, 3, 4, 1, 6, 5, 2, 7)
+    u = _winograd43_u(weight).reshape(cout // 64, 4, 16, cin // 8, 2, 4, 9, 4).permute(0, 3, 4, 1, 6, 5, 2, 7)
     return u.contiguous()
 
 

@@ -300,20 +300,21 @@ FAMILIES = {f.name: f for f in [
     # conv_winograd.hip:34-36 kWgCi = 8, kWgCo = 32, kWgTR x kWgTC = 4 x 16 tiles of 2 x 2 outputs
     Family("wino23", "conv3x3_winograd_bias_relu", "pack_winograd_weight", "winograd_supported",
            "pd3_conv3x3_winograd_bias_relu", (8, 32, 32, 8), "conv_winograd.hip:34-36", "nchw3", cout0=32, pitch_ok=False),
-    # conv_winograd43.hpp:11-12 kW4Ci = 4, kW4TR x kW4TC = 2 x 16 tiles of 4 x 4 outputs; channels per workgroup 32 / 64
+    # conv_winograd43.hpp:16-17 kW4Ci = 4, kW4TR x kW4TC = 2 x 16 tiles of 4 x 4 outputs; channels per workgroup 32 / 64
     Family("wino43_t32", "conv3x3_winograd43_bias_relu", "pack_winograd43_weight", "winograd43_supported",
-           "pd3_conv3x3_winograd43_bias_relu", (8, 64, 32, 4), "conv_winograd43.hpp:11-12", "nchw3", exact="wino43",
+           "pd3_conv3x3_winograd43_bias_relu", (8, 64, 32, 4), "conv_winograd43.hpp:16-17", "nchw3", exact="wino43",
            cin0=4, cout0=32, opts=dict(tile=32), extra_channels=((60, 32), (64, 32))),
     Family("wino43_t64", "conv3x3_winograd43_bias_relu", "pack_winograd43_weight", "winograd43_supported",
-           "pd3_conv3x3_winograd43_bias_relu", (8, 64, 64, 4), "conv_winograd43.hpp:11-12", "nchw3", exact="wino43",
+           "pd3_conv3x3_winograd43_bias_relu", (8, 64, 64, 4), "conv_winograd43.hpp:16-17", "nchw3", exact="wino43",
            cin0=4, cout0=64, opts=dict(tile=64), extra_channels=((60, 64), (64, 64), (64, 448), (64, 512))),
-    # conv_winograd43_pp.hip:52-53 kPpCi = 8 (two trips of kW4Ci), 64 channels per workgroup, the packed form's pixel tile
+    # conv_winograd43_pp.hpp:8-9 kPpCi = 8 (two trips of kW4Ci), 64 channels per workgroup, the packed form's pixel tile
     Family("wino43_pp", "conv3x3_winograd43_pp_bias_relu", "pack_winograd43_lane_weight", "winograd43_pp_supported",
-           "pd3_conv3x3_winograd43_pp_bias_relu", (8, 64, 64, 8), "conv_winograd43_pp.hip:52-53", "nchw3", exact="wino43",
+           "pd3_conv3x3_winograd43_pp_bias_relu", (8, 64, 64, 8), "conv_winograd43_pp.hpp:8-9", "nchw3", exact="wino43",
            extra_channels=((56, 64), (64, 64), (64, 448), (64, 512), (64, 1152), (64, 1216))),
-    # conv_winograd43_ppv.hip:21-26 kPvCi = 8, kPvMaxBlocks = 18 channel blocks per workgroup walk
+    # conv_winograd43_pp.hpp:8-9 kPpCi = 8; conv_winograd43_ppv.hip:22 kPvMaxBlocks = 18 channel blocks per workgroup walk
     Family("wino43_ppv", "conv3x3_winograd43_ppv_bias_relu", "pack_winograd43_lane_weight", "winograd43_pp_supported",
-           "pd3_conv3x3_winograd43_ppv_bias_relu", (8, 64, 64, 8), "conv_winograd43_ppv.hip:21-26", "nchw3", exact="wino43",
+           "pd3_conv3x3_winograd43_ppv_bias_relu", (8, 64, 64, 8), "conv_winograd43_pp.hpp:8-9,conv_winograd43_ppv.hip:22",
+           "nchw3", exact="wino43",
            extra_channels=((56, 64), (64, 64), (64, 448), (64, 512), (64, 1152), (64, 1216))),
     # conv_s2_x3.hip:26-27 kS2M = 128, kS2K = 48 (3 kx x 16 channels); :269-270 tiles of 8 x 32 output pixels
     Family("s2_x3", "conv3x3_s2_x3_bias_relu", "pack_conv3x3_s2_x3_weight", "conv3x3_s2_x3_supported",

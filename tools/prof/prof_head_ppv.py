@@ -1,7 +1,7 @@
 """CenterHead's first stage (64 -> 2304 as two slices of 1152) at CenterPoint-Pillars size, 16 frames: the ping-pong Winograd
 kernel against the form with the input transform computed once (conv_winograd43_ppv.hip)."""
-import sys, torch
-sys.path.insert(0, '/root/repo')
+import os, sys, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from paddle3d_amd.ops import conv
 torch.manual_seed(0)
 def timed(f, reps=10):
