@@ -976,6 +976,16 @@ int pd3_grouped_conv3x3_small(const float *x, const float *w_grouped, const floa
 int pd3_grouped_conv3x3_small_slice(const float *x, const float *w_grouped, const float *bias, int batch, int groups,
                                     int cin_per_group, int cout_per_group, int h, int w, float *out, int out_groups,
                                     int out_group0, void *stream);
+/* The slice form for groups whose real output-channel counts differ: group g has group_couts[g] real channels (1 ..
+ * cout_per_group; a HOST array of `groups` ints, at most 64, copied into the kernel's arguments -- no device memory, the
+ * launch can be captured in a graph).  Weights, bias and out keep the padded layout of the slice form (cout_per_group
+ * channels per group); a workgroup multiplies its group's real channels only and stores +0.0 to the padded ones, so every
+ * byte of the slice is written and equals what pd3_grouped_conv3x3_small_slice writes for zero padded weights and bias
+ * (finite inputs).  The input tile reaches LDS by buffer_load ... lds, double-buffered.
+ *   requires also groups <= 64 and 4 * h * w < 2^29 (else -3) */
+int pd3_grouped_conv3x3_small_counts_slice(const float *x, const float *w_grouped, const float *bias, int batch, int groups,
+                                           int cin_per_group, int cout_per_group, const int *group_couts, int h, int w,
+                                           float *out, int out_groups, int out_group0, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * conv3x3_winograd_bias_relu -- the same stride-1 convolution as conv3x3_bias_relu computed by Winograd

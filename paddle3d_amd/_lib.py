@@ -245,6 +245,18 @@ _SIGNATURES_ROI = {
 
 SYMBOLS_ROI = tuple(_SIGNATURES_ROI)
 
+# The final SeparateHead convolutions with per-group channel counts (csrc/conv3x3.hip).  A table of its own for the same
+# reason: its guarded scenarios and the completeness assertion over SYMBOLS_HEAD are in tests/test_grouped_counts_gpu.py.
+# (Tables per test file do not scale: the plan is ONE table whose entries name the test module that holds their scenarios,
+# with each completeness assertion filtering on that name; it needs the two existing memory-safety files changed together.)
+_SIGNATURES_HEAD = {
+    "pd3_grouped_conv3x3_small_counts_slice": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                                         C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                                         C.c_int, C.c_void_p]),
+}
+
+SYMBOLS_HEAD = tuple(_SIGNATURES_HEAD)
+
 
 class Paddle3DAmdError(RuntimeError):
     pass
@@ -257,7 +269,8 @@ def lib() -> C.CDLL:
             f"{LIB_PATH} not found: build it with `python -m paddle3d_amd.build` "
             "(there is no CPU / PyTorch fallback for the HIP ops)")
     handle = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(_SIGNATURES.items()) + list(_SIGNATURES_ROI.items()):
+    for name, (res, args) in (list(_SIGNATURES.items()) + list(_SIGNATURES_ROI.items()) +
+                              list(_SIGNATURES_HEAD.items())):
         try:
             fn = getattr(handle, name)
         except AttributeError as e:  # pragma: no cover

@@ -32,6 +32,7 @@ def _sources():
 def _headers():
     hs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")]
     hs.append(os.path.join(HERE, "..", "include", "paddle3d_amd.h"))
+    hs.append(os.path.abspath(__file__))  # the flags are in here
     return hs
 
 
@@ -42,9 +43,11 @@ def _stale(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-# per-file additions: the ping-pong Winograd kernel computes U = G g G^T next to its MFMAs, where the SLP vectoriser's
-# v_pk_* forms (two issue passes each, plus the v_mov shuffles that feed them) cost more than scalar VALU
-EXTRA_FLAGS = {}
+# per-file additions.  The two F(4x4, 3x3) ping-pong kernels are compiled without the SLP vectoriser: in their output step
+# A^T M A (and in the pair transform) every v_pk_add_f32 / v_pk_fma_f32 it forms is fed by two to four v_mov_b32 that gather
+# its operands, which costs more issue slots than the scalar instructions it replaces (the precomputed-V kernel: 672
+# v_mov_b32 with it, 2 without).  The packed ops compute what the scalar ones do: the bytes out do not change.
+EXTRA_FLAGS = {"conv_winograd43_pp.hip": ["-fno-slp-vectorize"], "conv_winograd43_ppv.hip": ["-fno-slp-vectorize"]}
 
 
 def _compile(src, force):

@@ -833,8 +833,13 @@ class CenterHead(_InferenceCache, nn.Module):
                                                            (c1 - c0) * 64, relu=True, out=y)
                 else:
                     wino(x, u[c0:c1], first.b[c0 * 64:c1 * 64], (c1 - c0) * 64, relu=True, out=y)
+                # the final convolutions of a slice with their real channel counts (70 of the head's 108 padded ones); the
+                # counts travel in the kernel arguments, 64 at most: a slice of more groups runs the padded kernel (same
+                # bytes, the zero weights multiplied)
                 _conv.grouped_conv3x3_small(y, f["pf"][c0:c1], f["bf"][c0 * f["cmax"]:c1 * f["cmax"]], c1 - c0, out=z,
-                                            out_groups=groups, out_group0=c0)
+                                            out_groups=groups, out_group0=c0,
+                                            group_couts=(f["ncls"][c0:c1]
+                                                         if c1 - c0 <= _conv.GROUPED_COUNTS_MAX_GROUPS else None))
         else:
             y, _ = first(x)
             z = _conv.grouped_conv3x3_small(y, f["pf"], f["bf"], groups)

@@ -21,6 +21,7 @@
 // The epilogue adds the bias, applies ReLU and writes 128-byte row segments.
 #include "../../include/paddle3d_amd.h"
 #include "common.hpp"
+#include "lds_dma.hpp"
 
 
 namespace pd3 {
@@ -269,6 +270,7 @@ static int launch_conv3x3(int64_t tiles, hipStream_t s, const float* x, const fl
 constexpr int kGcCi = 4;              // input channels staged per trip
 constexpr int kGcR = 8, kGcW = 128;   // pixel tile
 constexpr int kGcXR = kGcR + 2, kGcXW = kGcW + 8;
+constexpr int kGcMaxGroups = 64;      // groups of one launch of the per-group-count form (their counts: kernel arguments)
 
 template <int CO>
 __global__ __launch_bounds__(256) void grouped_conv3x3_small_kernel(const float* __restrict__ x,
@@ -358,6 +360,132 @@ __global__ __launch_bounds__(256) void grouped_conv3x3_small_kernel(const float*
       *reinterpret_cast<cv_f32x4*>(out + ((int64_t)n * out_groups * CO + (out_group0 + g) * CO + c) * plane +
                                    (int64_t)(y0 + tr) * w + x0 + tc) = v;
   }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// The same convolution for groups whose REAL output-channel counts differ (CenterHead: 70 real channels in 36 groups padded
+// to 3 each): same weight packing [groups][cg][CO][9], same output layout [n, groups * CO, h, w], same sums in the same
+// order for every real channel -- the same bytes as grouped_conv3x3_small_kernel, which multiplies the padding's zero
+// weights (35 % of the head's v_pk_fma_f32); here a workgroup runs the loop of its group's count and stores +0.0 to the
+// padded channels (what 0 + 0 * x + 0 bias gives for finite x).
+// Staging: the input tile goes from global memory straight into LDS (buffer_load_dwordx4 ... lds; padding: offsets beyond
+// the buffer's range read zeros), two buffers: trip t + 1 travels while trip t is multiplied, no staging registers, no
+// ds_write pass, ONE barrier per trip that orders LDS traffic only (w4_lds_barrier).  Tiles are 16 x 128 pixels on 512
+// threads (8-row tiles on 256 threads: 2.8 % slower than the padded kernel; these: 10 % faster), 79 872 B of LDS: 2
+// workgroups per CU.
+constexpr int kGnR = 16, kGnXR = kGnR + 2, kGnT = kGnR * 32;  // tile rows, staged rows (halo 1.125x), threads
+constexpr int kGcBuf = (kGcCi * kGnXR * kGcXW / 4 + 63) / 64 * 256;  // floats of one staging buffer: whole pieces of 64 float4
+struct gc_counts {
+  int n[kGcMaxGroups];
+};
+
+template <int CO, int NC>
+__device__ __forceinline__ void grouped_counts_body(const float* __restrict__ x, const float* __restrict__ wg,
+                                                    const float* __restrict__ bias, float* __restrict__ out,
+                                                    const int groups, const int cg, const int h, const int w,
+                                                    const int out_groups, const int out_group0, float* Xs, const int pt,
+                                                    const int g) {
+  constexpr int XQ = kGcXW / 4, XN4 = kGcCi * kGnXR * XQ;  // 2448 float4 per trip
+  constexpr int XPT = (XN4 + kGnT - 1) / kGnT;             // 5 per thread (39 pieces of 64 per trip, the last one partial)
+  const int tiles_x = (w + kGcW - 1) / kGcW, tiles_y = (h + kGnR - 1) / kGnR;
+  const int tx = pt % tiles_x, ty = (pt / tiles_x) % tiles_y, n = pt / (tiles_x * tiles_y);
+  const int y0 = ty * kGnR, x0 = tx * kGcW;
+  const int tr = threadIdx.x >> 5, tc = (threadIdx.x & 31) * 4;  // pixel row, first pixel column of the thread
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t plane = (int64_t)h * w;
+  const float* xin = x + ((int64_t)n * groups + g) * cg * plane;
+  const float* wgp = wg + (int64_t)g * cg * CO * 9;  // [cg][CO][9]
+  float acc[NC][4];
+#pragma unroll
+  for (int c = 0; c < NC; ++c)
+#pragma unroll
+    for (int p = 0; p < 4; ++p) acc[c][p] = 0.f;
+  // staging pattern (identical for every trip): float4 e = thread + 512 i of the tile comes from byte offset gofs[i] of the
+  // trip's four channel planes, or from beyond them (-> zeros) for the padding
+  unsigned gofs[XPT];
+#pragma unroll
+  for (int i = 0; i < XPT; ++i) {
+    const int e = min((int)threadIdx.x + i * kGnT, XN4 - 1);
+    const int ci = e / (kGnXR * XQ), rem = e - ci * (kGnXR * XQ);
+    const int r = rem / XQ, c4 = rem - r * XQ;
+    const int gy = y0 - 1 + r, gx = x0 - 4 + c4 * 4;
+    const bool ok = gy >= 0 && gy < h && gx >= 0 && gx < w;
+    gofs[i] = ok ? (unsigned)(4 * (ci * plane + (int64_t)gy * w + gx)) : 0x7ffffff0u;
+  }
+  // (the last piece is partial: float4 2432 .. 2447 of 2496; its other lanes are masked out and a masked lane of
+  // buffer_load ... lds writes nothing -- and a buffer is 39 whole pieces long, so it would stay inside it if it did)
+  auto fetch = [&](const int c0) {  // trip c0 / 4 into buffer (c0 / 4) & 1
+    float* dst = Xs + ((c0 / kGcCi) & 1) * kGcBuf + wave * 256;
+#pragma unroll
+    for (int i = 0; i < XPT; ++i)
+      if ((i + 1) * kGnT <= XN4 || (int)threadIdx.x + i * kGnT < XN4)
+        pp_dma(xin + (int64_t)c0 * plane, (unsigned)(kGcCi * plane * 4), dst + i * kGnT * 4, gofs[i], 0);
+  };
+  fetch(0);
+  for (int c0 = 0; c0 < cg; c0 += kGcCi) {
+    __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0): this wave's pieces of the trip have landed
+    w4_lds_barrier();                    // everybody's have, and everybody is done reading the other buffer
+    if (c0 + kGcCi < cg) fetch(c0 + kGcCi);
+    const float* Xb = Xs + ((c0 / kGcCi) & 1) * kGcBuf;
+#pragma unroll
+    for (int ci = 0; ci < kGcCi; ++ci) {
+      const float* wc = wgp + (int64_t)(c0 + ci) * CO * 9;
+#pragma unroll
+      for (int ky = 0; ky < 3; ++ky) {
+        // input columns tc-1 .. tc+4 of row tr+ky live at LDS columns tc+3 .. tc+8
+        const float* row = Xb + (ci * kGnXR + tr + ky) * kGcXW + tc;
+        const cv_f32x4 mid = *reinterpret_cast<const cv_f32x4*>(row + 4);
+        float in[6];
+        in[1] = mid[0];
+        in[2] = mid[1];
+        in[3] = mid[2];
+        in[4] = mid[3];
+        in[0] = row[3];
+        in[5] = row[8];
+#pragma unroll
+        for (int c = 0; c < NC; ++c)
+#pragma unroll
+          for (int kx = 0; kx < 3; ++kx) {
+            const float wv = wc[c * 9 + ky * 3 + kx];
+#pragma unroll
+            for (int p = 0; p < 4; ++p) acc[c][p] = __builtin_fmaf(wv, in[p + kx], acc[c][p]);
+          }
+      }
+    }
+  }
+  if (y0 + tr >= h || x0 + tc >= w) return;  // partial tiles at the border (w % 4 == 0: a quad is in or out)
+  float* o = out + ((int64_t)n * out_groups * CO + (out_group0 + g) * CO) * plane + (int64_t)(y0 + tr) * w + x0 + tc;
+#pragma unroll
+  for (int c = 0; c < CO; ++c) {
+    cv_f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (c < NC) {
+      const float b = bias ? bias[g * CO + c] : 0.f;
+      v = (cv_f32x4){acc[c][0] + b, acc[c][1] + b, acc[c][2] + b, acc[c][3] + b};
+    }
+    *reinterpret_cast<cv_f32x4*>(o + c * plane) = v;
+  }
+}
+
+template <int CO>
+__global__ __launch_bounds__(kGnT) void grouped_conv3x3_small_counts_kernel(const float* __restrict__ x,
+                                                                            const float* __restrict__ wg,
+                                                                            const float* __restrict__ bias,
+                                                                            float* __restrict__ out, int groups, int cg,
+                                                                            int h, int w, int out_groups, int out_group0,
+                                                                            const gc_counts counts) {
+  __shared__ __attribute__((aligned(16))) float Xs[2 * kGcBuf];
+  // (group-major order.  Tile-major with the tiles the first stage wrote last read first: 6 % slower, 489 against 461 us)
+  const int g = blockIdx.y, pt = blockIdx.x;
+  const int nc = counts.n[g];  // (uniform: one loop per workgroup)
+#define PD3_GCB(NC)                                                                                              \
+  if constexpr (NC <= CO)                                                                                        \
+    if (nc == NC)                                                                                                \
+    return grouped_counts_body<CO, NC>(x, wg, bias, out, groups, cg, h, w, out_groups, out_group0, Xs, pt, g)
+  PD3_GCB(1);
+  PD3_GCB(2);
+  PD3_GCB(3);
+  PD3_GCB(4);
+#undef PD3_GCB
 }
 
 }  // namespace pd3
@@ -459,4 +587,35 @@ extern "C" int pd3_grouped_conv3x3_small_slice(const float* x, const float* w_gr
                                                float* out, int out_groups, int out_group0, void* stream) {
   return grouped_small_launch(x, w_grouped, bias, batch, groups, cin_per_group, cout_per_group, h, w, out, out_groups,
                               out_group0, stream);
+}
+
+extern "C" int pd3_grouped_conv3x3_small_counts_slice(const float* x, const float* w_grouped, const float* bias,
+                                                      int batch, int groups, int cin_per_group, int cout_per_group,
+                                                      const int* group_couts, int h, int w, float* out, int out_groups,
+                                                      int out_group0, void* stream) {
+  if (!x || !w_grouped || !out || !group_couts || batch <= 0 || groups <= 0 || cin_per_group <= 0 || h <= 0 || w <= 0 ||
+      out_group0 < 0 || out_group0 + groups > out_groups)
+    return PD3_EINVAL;
+  if (cout_per_group < 1 || cout_per_group > 4 || cin_per_group % kGcCi != 0 || w % 4 != 0 || groups > kGcMaxGroups)
+    return PD3_EUNSUPPORTED;
+  if ((int64_t)kGcCi * h * w >= (int64_t)1 << 29) return PD3_EUNSUPPORTED;  // 32-bit byte offsets inside a trip's planes
+  if (reinterpret_cast<uintptr_t>(x) % 16 != 0 || reinterpret_cast<uintptr_t>(out) % 16 != 0) return PD3_EINVAL;
+  gc_counts counts = {};
+  for (int g = 0; g < groups; ++g) {
+    if (group_couts[g] < 1 || group_couts[g] > cout_per_group) return PD3_EINVAL;
+    counts.n[g] = group_couts[g];
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  dim3 grid((unsigned)((int64_t)batch * ceil_div(h, kGnR) * ceil_div(w, kGcW)), (unsigned)groups);
+#define PD3_GC(CO)                                                                                                   \
+  grouped_conv3x3_small_counts_kernel<CO><<<grid, kGnT, 0, s>>>(x, w_grouped, bias, out, groups, cin_per_group, h, w, \
+                                                                out_groups, out_group0, counts)
+  switch (cout_per_group) {
+    case 1: PD3_GC(1); break;
+    case 2: PD3_GC(2); break;
+    case 3: PD3_GC(3); break;
+    default: PD3_GC(4); break;
+  }
+#undef PD3_GC
+  return launch_status();
 }

@@ -5,6 +5,7 @@
 #pragma once
 #include "../../include/paddle3d_amd.h"
 #include "common.hpp"
+#include "lds_dma.hpp"
 
 #include <type_traits>
 
@@ -50,11 +51,7 @@ __device__ __forceinline__ float w4_swap_pair(float v) {  // value of the neighb
   return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, true));
 }
 
-// Workgroup barrier that orders LDS traffic only.  __syncthreads() makes the compiler drain vmcnt as well -- a pending
-// buffer_load ... lds counts as a store to LDS -- which puts the full latency of every fetch in flight in front of the
-// barrier.  The kernels that use this wait for exactly the fetches a barrier has to publish (explicit s_waitcnt vmcnt(N))
-// and let the others travel across it (LDS-DMA requests stay in flight across s_barrier).
-__device__ __forceinline__ void w4_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// (w4_lds_barrier, the workgroup barrier that orders LDS traffic only: lds_dma.hpp)
 
 // V = B^T d B of a thread pair's patch, from the six rows of this lane's three columns (rv[b][r] = d[r][3 hf + b]) to the
 // lane's 18 components at v.  Row pass on this lane's three columns, halves swapped between the pair, column pass on this
@@ -97,11 +94,12 @@ __device__ inline void w4_pair_transform(const float (&rv)[3][6], const int hf, 
 // N groups of 4 components (9 per trip of 4 input channels): b128 reads feed four MFMAs each; the reads run two groups
 // ahead of their MFMAs (ring of three).  B of group g is read from vptr(g).  A is either an array of N float4 already
 // in registers, or a functor g -> LDS address, read through a second ring.  hook() runs behind group HOOK's MFMAs (none
-// by default).
+// by default).  FIRST: the stream opens the sum -- the MFMAs of its first trip take a zero C operand (an inline constant)
+// instead of reading acc[], which nobody then has to clear: 0 + a * b either way.
 struct w4_no_hook {
   __device__ __forceinline__ void operator()() const {}
 };
-template <int N, int HOOK = -1, class UA, class VP, class F = w4_no_hook>
+template <int N, int HOOK = -1, bool FIRST = false, class UA, class VP, class F = w4_no_hook>
 __device__ __forceinline__ void w4_mfma_stream(w4_f32x4 (&acc)[36], const UA& ua, const VP& vptr, const F& hook = F()) {
   constexpr bool kRing = !std::is_array<UA>::value;
   w4_f32x4 a[3], b[3];
@@ -120,7 +118,9 @@ __device__ __forceinline__ void w4_mfma_stream(w4_f32x4 (&acc)[36], const UA& ua
       float av;
       if constexpr (kRing) av = a[g % 3][j];
       else av = ua[g][j];
-      acc[(g % 9) * 4 + j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b[g % 3][j], acc[(g % 9) * 4 + j], 0, 0, 0);
+      const w4_f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+      acc[(g % 9) * 4 + j] =
+          __builtin_amdgcn_mfma_f32_16x16x4f32(av, b[g % 3][j], FIRST && g < 9 ? zero : acc[(g % 9) * 4 + j], 0, 0, 0);
     }
     __builtin_amdgcn_sched_barrier(0);
     if (g == HOOK) {
@@ -133,6 +133,10 @@ __device__ __forceinline__ void w4_mfma_stream(w4_f32x4 (&acc)[36], const UA& ua
 // Output step: Y = A^T M A in registers, + bias, ReLU, zeros from column wv on, one non-temporal float4 store per output
 // row (16 lanes = 256 contiguous bytes).  The lane holds all 36 components of tile (oy, ox) for channels co0 + r (acc[c][r],
 // bias bv[r]).
+// RELU: 1 / 0 when the caller knows it at compile time, -1: the runtime flag `relu`.  WHOLE: the caller vouches for
+// wv == w, h % 8 == 0 and w % 64 == 0 -- no column is masked and no store is skipped, so neither is tested.  The general
+// form (-1, false) computes the same values: the fast paths only drop selects that would not have changed anything.
+template <int RELU = -1, bool WHOLE = false>
 __device__ __forceinline__ void w4_output_step(const w4_f32x4 (&acc)[36], const w4_f32x4 bv, const int n, const int cout,
                                                const int co0, const int oy, const int ox, const int h, const int w,
                                                const int wv, const int relu, const int64_t plane,
@@ -156,10 +160,10 @@ __device__ __forceinline__ void w4_output_step(const w4_f32x4 (&acc)[36], const 
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         y4[j] += bv[r];
-        if (relu) y4[j] = fmaxf(y4[j], 0.f);
-        if (ox + j >= wv) y4[j] = 0.f;
+        if (RELU < 0 ? relu != 0 : RELU != 0) y4[j] = fmaxf(y4[j], 0.f);
+        if (!WHOLE && ox + j >= wv) y4[j] = 0.f;
       }
-      if (oy + k < h && ox < w)  // partial tiles at the border (w % 4 == 0: a quad is in or out)
+      if (WHOLE || (oy + k < h && ox < w))  // partial tiles at the border (w % 4 == 0: a quad is in or out)
         __builtin_nontemporal_store((w4_f32x4){y4[0], y4[1], y4[2], y4[3]},
                                     reinterpret_cast<w4_f32x4*>(o + (int64_t)k * w));
     }
@@ -192,6 +196,9 @@ inline int w4_check_args(const void* in, const void* u, const void* out, int bat
     return PD3_EINVAL;
   return PD3_OK;
 }
+
+// can the output step take its WHOLE form?
+inline bool w4_whole(int h, int w, int w_valid) { return w_valid == w && h % (4 * kW4TR) == 0 && w % (4 * kW4TC) == 0; }
 
 // pixel tiles of a layer (-> *ptiles) and the workgroups of a launch that gives each of them `groups` channel groups: pixel
 // tiles rounded up to whole rounds of the 8 XCDs

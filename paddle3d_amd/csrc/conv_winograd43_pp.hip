@@ -55,6 +55,11 @@ constexpr int kPpRawPl = kPpRawR * kW4RawW;                // 432 floats per cha
 constexpr int kPpRawSz = kPpCi * kPpRawPl;                 // 3456 floats per group
 constexpr int kPpXPT = (2 * kPpRawPl / 4 + 63) / 64;       // 4 fetch pieces per wave: its two planes are 216 float4
 
+// DBG: the cycle stamps of pd3_conv3x3_winograd43_pp_trace (the production kernel carries none of it); RELU, WHOLE: the
+// output step's compile-time forms (w4_output_step).  The WHOLE kernels also open their sums with slot 0's MFMAs (zero C
+// operand) instead of clearing 144 registers; the general form, with the registers its masks take, spills more that way
+// than with the moves (8 dwords against 4) and keeps them.
+template <bool DBG, int RELU, bool WHOLE>
 __global__ __launch_bounds__(512, 1) void conv3x3_winograd43_pp_kernel(const float* __restrict__ x,
                                                                        const float* __restrict__ ulane,
                                                                        const float* __restrict__ bias,
@@ -62,7 +67,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winograd43_pp_kernel(const flo
                                                                        int w, int wv, int relu, int ptiles,
                                                                        long long* __restrict__ dbg) {
   constexpr int CO = 64;
-  long long t_tr = 0, t_mu = 0, t_ba = 0, t_all = dbg ? clock64() : 0;  // phase cycles of this wave (measurement)
+  long long t_tr = 0, t_mu = 0, t_ba = 0, t_all = DBG ? clock64() : 0;  // phase cycles of this wave (measurement)
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int lane = lane_id(), wave = __builtin_amdgcn_readfirstlane(wave_id());  // (uniform: scalar slot control)
   const int grp = wave >> 2, cb = wave & 3;  // tile row / 16-channel block of this wave; waves w and w + 4 share a SIMD
@@ -70,6 +75,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winograd43_pp_kernel(const flo
   float* Us = smem;                                          // [2 trips][4 cb][9][64 lanes][4]: U of the current slot
   float* Raw = smem + kPpUsz + grp * (kPpRawSz + kPpVsz);    // [8 ci][6 rows][72 cols] of this group's tile row
   float* Vs = Raw + kPpRawSz;                      // [8 ci][16 tiles][36]
+  float* bias_s = smem + kPpUsz + 2 * (kPpRawSz + kPpVsz);  // [64]: the bias of this workgroup's channels
   const w4_tile tl = w4_decode_block(cout / CO, h, w);
   if (tl.pt >= ptiles) return;
   const int ct = tl.cg, n = tl.n, y0 = tl.y0, x0 = tl.x0;
@@ -100,9 +106,12 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winograd43_pp_kernel(const flo
   const int bbase = pp_bbase(lane);
   const float* uct = ulane + (int64_t)ct * slots * kPpUsz;  // this workgroup's 64 output channels, all slots
 
+  constexpr bool PEEL = WHOLE;
   w4_f32x4 acc[36];
+  if constexpr (!PEEL) {
 #pragma unroll
-  for (int c = 0; c < 36; ++c) acc[c] = (w4_f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int c = 0; c < 36; ++c) acc[c] = (w4_f32x4){0.f, 0.f, 0.f, 0.f};
+  }
 
   // the wave's raw rows of slot s go from global memory straight into its planes of Raw (buffer_load_dwordx4 ... lds: no
   // staging registers, no store pass)
@@ -153,32 +162,37 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winograd43_pp_kernel(const flo
     __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0)
     read_rows();
   };
-  auto multiply_ring = [&]() { w4_mfma_stream<18, 15>(acc, uptr, vptr, next_rows); };
-  auto multiply_regs = [&]() { w4_mfma_stream<18, 16>(acc, ua, vptr, next_rows); };
+  auto multiply_ring = [&](auto first) { w4_mfma_stream<18, 15, decltype(first)::value>(acc, uptr, vptr, next_rows); };
+  auto multiply_regs = [&](auto first) { w4_mfma_stream<18, 16, decltype(first)::value>(acc, ua, vptr, next_rows); };
 
-  // prologue: the raw rows of slot 0 (each wave its own) and slot 0's U (group 0's waves, as in the loop)
+  // prologue: the raw rows of slot 0 (each wave its own), slot 0's U (group 0's waves, as in the loop) and the bias
+  if (threadIdx.x < CO) bias_s[threadIdx.x] = bias ? bias[ct * CO + threadIdx.x] : 0.f;
   fetch_x(0);
   if (grp == 0) {
     fetch_u(0, 0);
     fetch_u(0, 1);
   }
-  __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0)
-  read_rows();
-  w4_lds_barrier();
   // (every wave passes 2 * slots + 1 barriers: group 1 waits out the first time slot, group 0 the last)
   auto sync = [&]() {
-    const long long c1 = dbg ? clock64() : 0;
+    const long long c1 = DBG ? clock64() : 0;
     w4_lds_barrier();
-    if (dbg) t_ba += clock64() - c1;
+    if (DBG) t_ba += clock64() - c1;
   };
   // one straight-line loop per group (a single loop with the group's role chosen inside keeps two copies of the 144
-  // accumulators alive across the join and spills)
+  // accumulators alive across the join and spills), the output step inside it (behind a common join the compiler copies
+  // all 144 accumulators into one assignment: 145-150 v_mov_b32 per wave); slot 0 is peeled: its MFMAs open the sums
   auto run = [&](auto is_g0) {
     constexpr bool G0 = decltype(is_g0)::value;
+    if constexpr (PEEL) {
+      // (the first rows are read inside the group's copy: read in front of the branch they are spilled across it, 10 dwords)
+      __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0)
+      read_rows();
+      w4_lds_barrier();
+    }
     if (!G0) sync();
-    for (int s = 0; s < slots; ++s) {
+    auto slot = [&](const int s, auto first) {
       {  // transform slot s
-        const long long c0 = dbg ? clock64() : 0;
+        const long long c0 = DBG ? clock64() : 0;
         const int sn = min(s + 1, slots - 1);  // (the last slot's refetch is never read)
         if (G0) {
           // Us is free: group 0 read slot s - 1 through its ring in the time slot before this one, group 1 into ua[].
@@ -202,54 +216,70 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winograd43_pp_kernel(const flo
 #pragma unroll
           for (int g = 9; g < 18; ++g) ua[g] = *reinterpret_cast<const w4_f32x4*>(uptr(g));
         }
-        if (dbg) t_tr += clock64() - c0;
+        if (DBG) t_tr += clock64() - c0;
       }
       sync();
       {  // multiply slot s
-        const long long c0 = dbg ? clock64() : 0;
-        if (G0) multiply_ring();
-        else multiply_regs();
-        if (dbg) t_mu += clock64() - c0;
+        const long long c0 = DBG ? clock64() : 0;
+        if (G0) multiply_ring(first);
+        else multiply_regs(first);
+        if (DBG) t_mu += clock64() - c0;
       }
       sync();
-    }
+    };
+    if constexpr (PEEL) slot(0, std::true_type{});
+    for (int s = PEEL ? 1 : 0; s < slots; ++s) slot(s, std::false_type{});
     if (G0) sync();
+    if (DBG && blockIdx.x == 8 && lane == 0) {
+      dbg[wave * 4 + 0] = t_tr;
+      dbg[wave * 4 + 1] = t_mu;
+      dbg[wave * 4 + 2] = t_ba;
+      dbg[wave * 4 + 3] = (clock64() - t_all) | ((long long)__builtin_amdgcn_s_getreg(2308) << 56);  // + SIMD id (HW_ID[5:4])
+    }
+    // epilogue: lane: tile column lane & 15, channels 4 (lane >> 4) + r of the co block
+    const int cl = cb * 16 + 4 * (lane >> 4);
+    const w4_f32x4 bv = *reinterpret_cast<const w4_f32x4*>(bias_s + cl);
+    w4_output_step<RELU, WHOLE>(acc, bv, n, cout, ct * CO + cl, y0 + 4 * grp, x0 + 4 * (lane & 15), h, w, wv, relu, plane,
+                                out);
   };
+  if constexpr (!PEEL) {
+    __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0)
+    read_rows();
+    w4_lds_barrier();
+  }
   if (grp == 0) run(std::true_type{});
   else run(std::false_type{});
-  if (dbg && blockIdx.x == 8 && lane == 0) {
-    dbg[wave * 4 + 0] = t_tr;
-    dbg[wave * 4 + 1] = t_mu;
-    dbg[wave * 4 + 2] = t_ba;
-    dbg[wave * 4 + 3] = (clock64() - t_all) | ((long long)__builtin_amdgcn_s_getreg(2308) << 56);  // + SIMD id (HW_ID[5:4])
-  }
-
-  // epilogue: lane: tile column lane & 15, channels 4 (lane >> 4) + r of the co block
-  w4_f32x4 bv = {0.f, 0.f, 0.f, 0.f};
-  const int co0 = ct * CO + cb * 16 + 4 * (lane >> 4);
-  if (bias) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) bv[r] = bias[co0 + r];
-  }
-  w4_output_step(acc, bv, n, cout, co0, y0 + 4 * grp, x0 + 4 * (lane & 15), h, w, wv, relu, plane, out);
 }
 
 }  // namespace pd3
 
 using namespace pd3;
 
-static int launch_wino43_pp(const float* x, const float* u_lane, const float* bias, int batch, int cin, int cout, int h,
-                            int w, int w_valid, int relu, float* out, hipStream_t s, long long* dbg = nullptr) {
-  constexpr size_t lds = ((size_t)kPpUsz + 2 * (kPpRawSz + kPpVsz)) * sizeof(float);  // 138,240 B
-  const void* fn = reinterpret_cast<const void*>(conv3x3_winograd43_pp_kernel);
+template <bool DBG, int RELU, bool WHOLE>
+static int launch_wino43_pp_as(const float* x, const float* u_lane, const float* bias, int batch, int cin, int cout, int h,
+                               int w, int w_valid, int relu, float* out, hipStream_t s, long long* dbg) {
+  constexpr size_t lds = ((size_t)kPpUsz + 2 * (kPpRawSz + kPpVsz) + 64) * sizeof(float);  // 138,240 B + the bias
+  const void* fn = reinterpret_cast<const void*>(conv3x3_winograd43_pp_kernel<DBG, RELU, WHOLE>);
   hipError_t e = pd3_max_dynamic_lds(fn, (int)lds);
   if (e != hipSuccess) return (int)e;
   int64_t ptiles;
   const int64_t nwg = w4_grid(batch, h, w, cout / 64, &ptiles);
   if (nwg >= (int64_t)1 << 31) return PD3_EUNSUPPORTED;
-  conv3x3_winograd43_pp_kernel<<<(unsigned)nwg, 512, lds, s>>>(x, u_lane, bias, out, cin, cout, h, w, w_valid, relu,
-                                                               (int)ptiles, dbg);
+  conv3x3_winograd43_pp_kernel<DBG, RELU, WHOLE><<<(unsigned)nwg, 512, lds, s>>>(x, u_lane, bias, out, cin, cout, h, w,
+                                                                                 w_valid, relu, (int)ptiles, dbg);
   return launch_status();
+}
+
+// whole tiles at full width take the output step's compile-time forms, every other layer the general one; the traced
+// kernel is the form production picks for the same layer, with the stamps
+static int launch_wino43_pp(const float* x, const float* u_lane, const float* bias, int batch, int cin, int cout, int h,
+                            int w, int w_valid, int relu, float* out, hipStream_t s, long long* dbg = nullptr) {
+#define PD3_PP(DBG, RELU, WHOLE) \
+  launch_wino43_pp_as<DBG, RELU, WHOLE>(x, u_lane, bias, batch, cin, cout, h, w, w_valid, relu, out, s, dbg)
+  if (!w4_whole(h, w, w_valid)) return dbg ? PD3_PP(true, -1, false) : PD3_PP(false, -1, false);
+  if (dbg) return relu ? PD3_PP(true, 1, true) : PD3_PP(true, 0, true);
+  return relu ? PD3_PP(false, 1, true) : PD3_PP(false, 0, true);
+#undef PD3_PP
 }
 
 static int check_wino43_pp(const float* x, const float* u_lane, const float* out, int batch, int cin, int cout, int h,

@@ -11,12 +11,7 @@ constexpr int kPpVsz = kPpCi * kW4TC * kW4Cs;              // 4608 floats per (t
 constexpr int kPpUHalf = 9 * 64 * 4;                       // 2304 floats: U of one trip for one wave (9 float4 per lane)
 constexpr int kPpUsz = kPpKT * 4 * kPpUHalf;               // 18432 floats per slot: [trip][cb][q][lane][4]
 
-// 64 lanes x 16 bytes from base + voff + soff to lds .. lds + 1023 (buffer_load_dwordx4 ... lds: no staging registers, no
-// store pass; bytes from `bytes` on read as zeros)
-__device__ __forceinline__ void pp_dma(const float* base, unsigned bytes, float* lds, unsigned voff, unsigned soff) {
-  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, (int)bytes, 0x00020000);
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds, 16, (int)voff, (int)soff, 0, 0);
-}
+// (pp_dma, 64 lanes x 16 bytes from global memory straight into LDS: lds_dma.hpp)
 
 // MFMA operands of group g = 9 trip + q of a multiply slot: B = V[(trip * 4 + k) ci][tile][component] (bbase: the lane's
 // (k, tile) = (lane >> 4, lane & 15)); A = U of (co, ci) = (lane & 15, lane >> 4), float4 q of the lane's 36 components at

@@ -65,6 +65,8 @@ __global__ __launch_bounds__(128) void w43_input_transform_kernel(const float* _
   for (int i = 0; i < kPpVsz / 4 / 128; ++i) out4[threadIdx.x + i * 128] = b4[threadIdx.x + i * 128];
 }
 
+// RELU, WHOLE: the output step's compile-time forms (w4_output_step)
+template <int RELU, bool WHOLE>
 __global__ __launch_bounds__(512, 1) void conv3x3_winograd43_ppv_kernel(const float* __restrict__ vpre,
                                                                         const float* __restrict__ ulane,
                                                                         const float* __restrict__ bias,
@@ -93,9 +95,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winograd43_ppv_kernel(const fl
   const unsigned vbytes = (unsigned)(slots * 2 * kPpVsz * 4);
   const int nv = cb < 2 ? 5 : 4;
 
-  w4_f32x4 acc[36];
-#pragma unroll
-  for (int c = 0; c < 36; ++c) acc[c] = (w4_f32x4){0.f, 0.f, 0.f, 0.f};
+  w4_f32x4 acc[36];  // (opened by the zero C operand of every block's first multiply slot: nothing to clear)
 
   auto fetch_v = [&](int s) {
     float* dst = Vs + (s & 1) * kPpVsz;
@@ -115,8 +115,12 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winograd43_ppv_kernel(const fl
   // is waited for inside it)
   auto uptr = [&](int g) { return pp_uptr(Us, cb, lane, g); };
   w4_f32x4 ua[18];
-  auto multiply_ring = [&](const float* V) { w4_mfma_stream<18>(acc, uptr, [&](int g) { return pp_vptr(V, bbase, g); }); };
-  auto multiply_regs = [&](const float* V) { w4_mfma_stream<18>(acc, ua, [&](int g) { return pp_vptr(V, bbase, g); }); };
+  auto multiply_ring = [&](const float* V, auto first) {
+    w4_mfma_stream<18, -1, decltype(first)::value>(acc, uptr, [&](int g) { return pp_vptr(V, bbase, g); });
+  };
+  auto multiply_regs = [&](const float* V, auto first) {
+    w4_mfma_stream<18, -1, decltype(first)::value>(acc, ua, [&](int g) { return pp_vptr(V, bbase, g); });
+  };
 
   // prologue: the bias of the workgroup's blocks, V of slot 0 (each group its own tile row) and slot 0's U (group 0's waves)
   for (int t = threadIdx.x; t < ipw * CO; t += 512) bias_s[t] = bias ? bias[ct0 * CO + t] : 0.f;
@@ -135,7 +139,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winograd43_ppv_kernel(const fl
   auto run = [&](auto is_g0) {
     constexpr bool G0 = decltype(is_g0)::value;
     if (!G0) w4_lds_barrier();
-    for (int s = 0; s < slots; ++s) {
+    auto slot = [&](const int s, auto first) {  // (slot 0 is peeled: its MFMAs open the block's sums)
       {  // "transform" slot s
         if (G0 && s > 0) {
           fetch_u(ct, s, 0);
@@ -161,11 +165,13 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winograd43_ppv_kernel(const fl
       w4_lds_barrier();
       {  // multiply slot s
         const float* V = Vs + (s & 1) * kPpVsz;
-        if (G0) multiply_ring(V);
-        else multiply_regs(V);
+        if (G0) multiply_ring(V, first);
+        else multiply_regs(V, first);
       }
       w4_lds_barrier();
-    }
+    };
+    slot(0, std::true_type{});
+    for (int s = 1; s < slots; ++s) slot(s, std::false_type{});
     if (G0) w4_lds_barrier();
   };
   // (one straight-line copy of the block loop per group: with the group's role chosen inside the loop the two roles'
@@ -186,10 +192,8 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winograd43_ppv_kernel(const fl
   // epilogue (as conv_winograd43_pp.hip): lane: tile column lane & 15, channels 4 (lane >> 4) + r of the block
   const int co0 = ct * CO + cb * 16 + 4 * (lane >> 4);
   const w4_f32x4 b4 = *reinterpret_cast<const w4_f32x4*>(bias_s + it * CO + cb * 16 + 4 * (lane >> 4));
-  w4_output_step(acc, b4, n, cout, co0, y0 + 4 * grp, x0 + 4 * (lane & 15), h, w, wv, relu, plane, out);
+  w4_output_step<RELU, WHOLE>(acc, b4, n, cout, co0, y0 + 4 * grp, x0 + 4 * (lane & 15), h, w, wv, relu, plane, out);
   if (it + 1 < ipw) {
-#pragma unroll
-    for (int c = 0; c < 36; ++c) acc[c] = (w4_f32x4){0.f, 0.f, 0.f, 0.f};
     // the next block's fetches have landed; younger than them are only this block's 16 stores per lane, which drain under
     // the next block's first slots -- where every wave issued all 16 (whole tiles); with partial tiles a wave may have
     // skipped some, and the count would let a fetch through: everything then
@@ -244,12 +248,20 @@ extern "C" int pd3_conv3x3_winograd43_ppv_bias_relu(const float* v_pre, const fl
   for (int d = 2; d <= kPvMaxBlocks; ++d)
     if (nct % d == 0 && ptiles8 * (nct / d) >= 6 * 256) ipw = d;
   const size_t lds = ((size_t)kPpUsz + 4 * kPpVsz + kPvMaxBlocks * 64) * sizeof(float);  // 147 456 B + the blocks' bias
-  const void* fn = reinterpret_cast<const void*>(conv3x3_winograd43_ppv_kernel);
-  const hipError_t e = pd3_max_dynamic_lds(fn, (int)lds);
-  if (e != hipSuccess) return (int)e;
   const int64_t nwg = ptiles8 * (nct / ipw);
   if (nwg >= (int64_t)1 << 31) return PD3_EUNSUPPORTED;
-  conv3x3_winograd43_ppv_kernel<<<(unsigned)nwg, 512, lds, static_cast<hipStream_t>(stream)>>>(
-      v_pre, u_lane, bias, out, cin, cout, h, w, w_valid, relu, (int)ptiles, ipw);
+  // whole tiles at full width take the output step's compile-time forms, every other layer the general one
+#define PD3_PV(RELU, WHOLE)                                                                                              \
+  do {                                                                                                                   \
+    const void* fn = reinterpret_cast<const void*>(conv3x3_winograd43_ppv_kernel<RELU, WHOLE>);                          \
+    const hipError_t e = pd3_max_dynamic_lds(fn, (int)lds);                                                              \
+    if (e != hipSuccess) return (int)e;                                                                                  \
+    conv3x3_winograd43_ppv_kernel<RELU, WHOLE><<<(unsigned)nwg, 512, lds, static_cast<hipStream_t>(stream)>>>(           \
+        v_pre, u_lane, bias, out, cin, cout, h, w, w_valid, relu, (int)ptiles, ipw);                                     \
+  } while (0)
+  if (!w4_whole(h, w, w_valid)) PD3_PV(-1, false);
+  else if (relu) PD3_PV(1, true);
+  else PD3_PV(0, true);
+#undef PD3_PV
   return launch_status();
 }

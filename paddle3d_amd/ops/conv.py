@@ -4,6 +4,8 @@ patch_conv_bias_relu (kernel = stride FPN levels, written at a channel offset), 
 SeparateHead convolutions), plus the host-side weight packers each kernel expects."""
 from __future__ import annotations
 
+import ctypes
+
 import torch
 
 from ._common import check, lib, ptr, require_gpu, stream_ptr
@@ -399,12 +401,17 @@ def pack_grouped_weight(weight: torch.Tensor, groups: int) -> torch.Tensor:
     return weight.reshape(groups, co, cg, 9).permute(0, 2, 1, 3).contiguous()
 
 
+GROUPED_COUNTS_MAX_GROUPS = 64  # groups of one pd3_grouped_conv3x3_small_counts_slice launch (kGcMaxGroups)
+
+
 def grouped_conv3x3_small(x: torch.Tensor, w_grouped: torch.Tensor, bias, groups: int,
                           out: torch.Tensor | None = None, out_groups: int | None = None,
-                          out_group0: int = 0) -> torch.Tensor:
+                          out_group0: int = 0, group_couts=None) -> torch.Tensor:
     """Grouped 3x3 convolution + bias with 1..4 output channels per group (the final SeparateHead convolutions).
     out_groups / out_group0: x, w_grouped and bias describe a slice of `groups` consecutive groups whose outputs land
-    at groups [out_group0, out_group0 + groups) of `out` [n, out_groups * co, h, w]."""
+    at groups [out_group0, out_group0 + groups) of `out` [n, out_groups * co, h, w].
+    group_couts: the real output-channel count of every group (the rest of its `co` are zero padding in w_grouped and
+    bias): the kernel multiplies the real channels only and writes +0.0 to the padding -- the same bytes."""
     xx = require_gpu(x, "grouped_conv3x3_small")
     n, c, h, w = xx.shape
     cg, co = w_grouped.shape[1], w_grouped.shape[2]
@@ -413,6 +420,13 @@ def grouped_conv3x3_small(x: torch.Tensor, w_grouped: torch.Tensor, bias, groups
     if out is None:
         out = torch.empty((n, total * co, h, w), dtype=torch.float32, device=xx.device)
     assert out.is_contiguous() and tuple(out.shape) == (n, total * co, h, w)
+    if group_couts is not None:
+        assert len(group_couts) == groups
+        counts = (ctypes.c_int * groups)(*[int(c) for c in group_couts])
+        check(lib().pd3_grouped_conv3x3_small_counts_slice(ptr(xx), ptr(w_grouped), ptr(bias), n, groups, cg, co, counts, h,
+                                                           w, ptr(out), total, int(out_group0), stream_ptr(xx.device)),
+              "grouped_conv3x3_small")
+        return out
     check(lib().pd3_grouped_conv3x3_small_slice(ptr(xx), ptr(w_grouped), ptr(bias), n, groups, cg, co, h, w, ptr(out),
                                                 total, int(out_group0), stream_ptr(xx.device)),
           "grouped_conv3x3_small")
