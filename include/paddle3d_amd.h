@@ -604,6 +604,49 @@ int pd3_class_agnostic_nms(const float *box_preds, const float *cls_preds, int b
                            size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * PV-RCNN's keypoint branch and RoI head (csrc/pvrcnn.hip).  Inference only.  fp32 data, int32 counts, contiguous
+ * tensors, 64-bit offsets inside the kernels, no float atomics; nothing here synchronises with the host.
+ *
+ * stack_sa_pool -- one scale of StackSAModuleMSG.forward (pointnet2_stack/pointnet2_modules.py:31-120) from the ball
+ * query to the max pool, with no [m, *, nsample] tensor and no idx in global memory.  The scale's mlp is
+ * Conv2d(3 + C -> c1) / BN / ReLU, Conv2d(c1 -> c2) / BN / ReLU; the first convolution is linear in [d; f], so the
+ * caller passes features_in = features @ W1[:, 3:]^T ([n, c1], NULL reads as zeros) and w_pos = W1[:, :3].
+ * new_xyz [m, 3], new_xyz_batch_cnt [batch], xyz [n, 3], xyz_batch_cnt [batch], w_pos [c1, 3], scale1 / shift1 [c1],
+ * w2 [c2, c1], scale2 / shift2 [c2] (each BatchNorm in eval form, scale = gamma / sqrt(var + eps), shift = beta -
+ * mean * scale, formed by the caller in fp32) -> pooled [m, c2]:
+ *   h[s, j]      = relu(scale1[j] * (features_in[row_s, j] + ((w_pos[j,0] * dx + w_pos[j,1] * dy) + w_pos[j,2] * dz))
+ *                       + shift1[j])                                                       (no FMA)
+ *   pooled[m, c] = max_s relu(scale2[c] * (sum_j w2[c, j] * h[s, j]) + shift2[c])          (no FMA outside the sum)
+ * with idx exactly pd3_ball_query_stack's row for the same arguments (the frame of a row, frame-local indices, the
+ * first nsample hits in index order, d2 < r2, a NaN is no hit), row_s = start(frame) + idx[s], d = xyz[row_s] -
+ * new_xyz.  A row without a hit takes features 0 and d 0: h[j] = relu(shift1[j]) (the reference's zeroed grouped
+ * tensor).  The sum over j is an ascending-j fp32 fmaf chain from 0 (what v_mfma_f32_16x16x4_f32 computes), so the
+ * result depends neither on the tiling nor on where a row sits in the launch.  The max runs over the hits only (unused
+ * slots repeat slot 0).  relu(v) = v > 0 ? v : +0 (a NaN stays) and the max keeps a NaN, as in pd3_voxel_pool.
+ * c1, c2 not in {16, 32, 64} or nsample > 64: PD3_EUNSUPPORTED; batch > 256 too.  PD3_EINVAL on negative dims,
+ * nsample < 1, or batch == 0 with rows to compute; m == 0 launches nothing.
+ */
+int pd3_stack_sa_pool(const float *new_xyz, const int *new_xyz_batch_cnt, const float *xyz, const int *xyz_batch_cnt,
+                      const float *features_in, const float *w_pos, const float *scale1, const float *shift1,
+                      const float *w2, const float *scale2, const float *shift2, int batch, int m, int n, int c1,
+                      int c2, float radius, int nsample, float *pooled, void *stream);
+
+/* bev_interpolate -- VoxelSetAbstraction.interpolate_from_bev_features with bilinear_interpolate_paddle
+ * (point_encoders/voxel_set_abstraction.py:32-67, 180-213) for all frames in one launch, reading the NCHW map in
+ * place.  keypoints [m, 4] as (b, x, y, z), bev [batch, channels, h, w] -> out [m, channels]:
+ *   xs = ((x - range_min_x) / voxel_x) / stride, ys likewise (true divisions, the reference's order);
+ *   x0 = floor(xs), x1 = x0 + 1, both clipped to [0, w - 1] (y to [0, h - 1]) BEFORE the weights are formed;
+ *   wa = (x1 - xs) * (y1 - ys), wb = (x1 - xs) * (ys - y0), wc = (xs - x0) * (y1 - ys), wd = (xs - x0) * (ys - y0);
+ *   out = ((Ia * wa + Ib * wb) + Ic * wc) + Id * wd, Ia = bev[b, :, y0, x0], Ib = [y1, x0], Ic = [y0, x1],
+ *   Id = [y1, x1].  No FMA.
+ * Departures: a frame index that is no integer of [0, batch) gives a zero row (the reference drops the row); a floor
+ * outside int32 saturates and a NaN is 0, as in pd3_roi_grid_points.  m * channels == 0 launches nothing.
+ */
+int pd3_bev_interpolate(const float *keypoints, const float *bev, int64_t m, int batch, int channels, int h, int w,
+                        float range_min_x, float range_min_y, float voxel_x, float voxel_y, float stride, float *out,
+                        void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * assign_score_withk / its gradient -- replace PD_BUILD_OP and PD_BUILD_GRAD_OP(assign_score_withk)
  * (assign_score_withk/assign_score_withk_cuda.cc:265-274, CPU kernels :32-158): PAConv's weight-bank assembly
  * (csrc/assign_score_withk.hip).  fp32 data, int64 knn_idx, contiguous tensors, 64-bit offsets.

@@ -257,6 +257,17 @@ _SIGNATURES_HEAD = {
 
 SYMBOLS_HEAD = tuple(_SIGNATURES_HEAD)
 
+# PV-RCNN's keypoint branch and RoI head (csrc/pvrcnn.hip).  The third table of this kind, for the same reason: its
+# guarded scenarios and the completeness assertion over SYMBOLS_PVRCNN are in tests/test_memory_safety_pvrcnn_gpu.py
+# (a copy of the RoI file's protocol; under the one-table plan above it becomes a module name in its entries).
+_SIGNATURES_PVRCNN = {
+    "pd3_stack_sa_pool": (C.c_int, [C.c_void_p] * 11 + [C.c_int] * 5 + [C.c_float, C.c_int] + [C.c_void_p] * 2),
+    "pd3_bev_interpolate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_int] * 4 + [C.c_float] * 5 +
+                            [C.c_void_p] * 2),
+}
+
+SYMBOLS_PVRCNN = tuple(_SIGNATURES_PVRCNN)
+
 
 class Paddle3DAmdError(RuntimeError):
     pass
@@ -270,7 +281,7 @@ def lib() -> C.CDLL:
             "(there is no CPU / PyTorch fallback for the HIP ops)")
     handle = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(_SIGNATURES.items()) + list(_SIGNATURES_ROI.items()) +
-                              list(_SIGNATURES_HEAD.items())):
+                              list(_SIGNATURES_HEAD.items()) + list(_SIGNATURES_PVRCNN.items())):
         try:
             fn = getattr(handle, name)
         except AttributeError as e:  # pragma: no cover

@@ -4,10 +4,15 @@ abstraction layers of PV-RCNN (StackSAModuleMSG) and Voxel R-CNN (NeighborVoxelS
 QueryAndGroup(radius, nsample, use_xyz)        pointnet2_utils.py:27-89: ball query, xyz relative to the centre,
                                                features, concat [xyz, features]; empty balls give zero idx, xyz and
                                                features.  -> (new_features [M, 3 + C, nsample], idx)
-StackSAModuleMSG(radii, nsamples, mlps, use_xyz, pool_method)
-build_local_aggregation_module(input_channels, config)
+StackSAModuleMSG(radii, nsamples, mlps, use_xyz, pool_method, fused=False)
+build_local_aggregation_module(input_channels, config, fused=False)
                                                pointnet2_modules.py:31-157: per radius a QueryAndGroup, a 1x1
                                                Conv2d / BN / ReLU stack and a max or avg pool over nsample.
+                                               fused=True: in eval mode without gradients, a max-pooled scale with
+                                               use_xyz whose mlp is Conv / BN / ReLU twice and whose (C1, C2, nsample)
+                                               the op takes runs from the ball query to the pool as
+                                               ops.pvrcnn.stack_sa_pool (no [M, *, nsample] tensor); every other case
+                                               runs the unfused forward.
 voxel_query(max_range, radius, nsample, xyz, new_xyz, new_coords, point_indices)
 VoxelQueryAndGrouping(max_range, radius, nsample)
                                                voxel_query_utils.py:28-106: the voxel query, its global indices made
@@ -33,7 +38,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from .ops import pointnet2_ops, roi_head
+from .ops import pointnet2_ops, pvrcnn, roi_head
 
 __all__ = ["QueryAndGroup", "StackSAModuleMSG", "build_local_aggregation_module", "voxel_query",
            "VoxelQueryAndGrouping", "NeighborVoxelSAModuleMSG", "generate_voxel2pinds"]
@@ -96,9 +101,11 @@ class QueryAndGroup(nn.Module):
 
 class StackSAModuleMSG(nn.Module):
     def __init__(self, *, radii: List[float], nsamples: List[int], mlps: List[List[int]], use_xyz: bool = True,
-                 pool_method: str = "max_pool"):
+                 pool_method: str = "max_pool", fused: bool = False):
         super().__init__()
         assert len(radii) == len(nsamples) == len(mlps)
+        self.fused = fused
+        self.use_xyz = use_xyz
         self.groupers = nn.ModuleList()
         self.mlps = nn.ModuleList()
         for radius, nsample, mlp_spec in zip(radii, nsamples, mlps):
@@ -113,19 +120,43 @@ class StackSAModuleMSG(nn.Module):
         self.pool_method = pool_method
         _init_weights(self)
 
+    def _takes_fused(self, k):
+        mlp, g = self.mlps[k], self.groupers[k]
+        return (self.fused and not self.training and not torch.is_grad_enabled() and self.use_xyz
+                and self.pool_method == "max_pool" and len(mlp) == 6
+                and pvrcnn.stack_sa_pool_supported(mlp[0].out_channels, mlp[3].out_channels, g.nsample))
+
+    def _fused_pool(self, k, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, features):
+        """[M, C2]: scale k from the ball query to the pool in one kernel.  The first convolution is linear in
+        [d; f]: its feature columns run once over the N source rows, its xyz columns go to the kernel; each
+        BatchNorm in eval form, scale = gamma / sqrt(var + eps), shift = beta - mean * scale, formed in fp32."""
+        mlp, g = self.mlps[k], self.groupers[k]
+        c1, c2 = mlp[0].out_channels, mlp[3].out_channels
+        w1 = mlp[0].weight.reshape(c1, -1)
+        features_in = None if features is None else features @ w1[:, 3:].t()
+        scale1 = mlp[1].weight / torch.sqrt(mlp[1].running_var + mlp[1].eps)
+        shift1 = mlp[1].bias - mlp[1].running_mean * scale1
+        scale2 = mlp[4].weight / torch.sqrt(mlp[4].running_var + mlp[4].eps)
+        shift2 = mlp[4].bias - mlp[4].running_mean * scale2
+        return pvrcnn.stack_sa_pool(new_xyz, new_xyz_batch_cnt, xyz, xyz_batch_cnt, features_in, w1[:, :3], scale1,
+                                    shift1, mlp[3].weight.reshape(c2, c1), scale2, shift2, g.radius, g.nsample)
+
     def forward(self, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, features=None, empty_voxel_set_zeros=True):
         """-> (new_xyz [M, 3], new_features [M, sum of mlps[k][-1]])."""
         out = []
-        for grouper, mlp in zip(self.groupers, self.mlps):
+        for k, (grouper, mlp) in enumerate(zip(self.groupers, self.mlps)):
+            if self._takes_fused(k):
+                out.append(self._fused_pool(k, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, features))
+                continue
             new_features, _ = grouper(xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, features)  # [M, C, nsample]
             new_features = mlp(new_features.permute(1, 0, 2).unsqueeze(0))  # [1, C', M, nsample]
             out.append(_pool(new_features, self.pool_method).squeeze(0).transpose(0, 1))  # [M, C']
         return new_xyz, torch.cat(out, dim=1)
 
 
-def build_local_aggregation_module(input_channels, config):
+def build_local_aggregation_module(input_channels, config, fused=False):
     """(StackSAModuleMSG, its output channels) from a config with mlps / pool_radius / nsample; config["mlps"] gets
-    input_channels prepended in place, as the reference's does."""
+    input_channels prepended in place, as the reference's does.  fused: StackSAModuleMSG's."""
     name = config.get("name", "StackSAModuleMSG")
     if name != "StackSAModuleMSG":
         raise NotImplementedError(name)
@@ -133,7 +164,7 @@ def build_local_aggregation_module(input_channels, config):
     for k in range(len(mlps)):
         mlps[k] = [input_channels] + mlps[k]
     layer = StackSAModuleMSG(radii=config["pool_radius"], nsamples=config["nsample"], mlps=mlps, use_xyz=True,
-                             pool_method="max_pool")
+                             pool_method="max_pool", fused=fused)
     return layer, sum(x[-1] for x in mlps)
 
 

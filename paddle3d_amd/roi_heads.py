@@ -21,6 +21,18 @@ post_processing(batch_dict, post_process_cfg, num_class, padded=False)
                                                detection/voxel_rcnn/voxel_rcnn.py:145-220: per frame box3d_lidar,
                                                scores, label_preds.
 voxel_rcnn_head_kitti_car()                    the head of configs/voxel_rcnn/voxel_rcnn_005voxel_kitti_car.yml.
+PVRCNNHead(input_channels, model_cfg, num_class, fused=None)
+                                               heads/roi_heads/pvrcnn_head.py:34-197 with the reference's sublayer names
+                                               (roi_grid_pool_layer, shared_fc_layer, cls_layers, reg_layers; the fc
+                                               stacks are Conv1d with kernel 1, as the reference's, so Paddle weight
+                                               shapes map).  forward(batch_dict): batch_size, batch_box_preds,
+                                               batch_cls_preds, point_coords, point_features, point_cls_scores -> as
+                                               VoxelRCNNHead.
+pv_rcnn_kitti(fused=None)                      VoxelSetAbstraction, PointHeadSimple and PVRCNNHead of
+                                               configs/pv_rcnn/pv_rcnn_005voxel_kitti.yml as a PVRCNNSecondStage;
+pv_rcnn_second_stage(batch_dict, model=None)   runs it without gradients (model None: one pv_rcnn_kitti() per
+                                               device, built at the first call).  post_processing serves both models
+                                               (detection/pv_rcnn/pv_rcnn.py:151-220 is voxel_rcnn.py's).
 
 Inference only: training (targets, losses) raises.  Dropout is the identity at inference and is left out of the
 Sequentials' arithmetic but kept in their numbering, so the Paddle sublayer indices hold.  Nothing in forward
@@ -36,13 +48,16 @@ import torch
 from torch import nn
 
 from .ops import roi_head as _ops
-from .pointnet2_stack import NeighborVoxelSAModuleMSG, generate_voxel2pinds
+from .pointnet2_stack import NeighborVoxelSAModuleMSG, build_local_aggregation_module, generate_voxel2pinds
 
 __all__ = ["ResidualCoder", "class_agnostic_nms", "RoIHeadBase", "VoxelRCNNHead", "post_processing",
-           "voxel_rcnn_head_kitti_car", "FUSED_POOL_DEFAULT"]
+           "voxel_rcnn_head_kitti_car", "FUSED_POOL_DEFAULT", "PVRCNNHead", "pv_rcnn_kitti", "pv_rcnn_second_stage", "pv_rcnn_kitti_stage",
+           "FUSED_SA_DEFAULT"]
 
 # Whether VoxelRCNNHead builds its pool layers with the fused voxel pool (DESIGN 4.5h has the measurement behind it).
 FUSED_POOL_DEFAULT = True
+# Whether pv_rcnn_kitti builds PV-RCNN's set abstraction layers with the fused stack pool.
+FUSED_SA_DEFAULT = False
 
 
 class ResidualCoder:
@@ -211,6 +226,84 @@ class VoxelRCNNHead(RoIHeadBase):
         return batch_dict
 
 
+def _conv_fc_stack(pre_channel, widths, dp_after):
+    """Conv1d(k = 1) / BN / ReLU per width; dp_after(k): whether the reference has a Dropout behind block k (an
+    Identity here: it holds the sublayer index)."""
+    layers = []
+    for k, w in enumerate(widths):
+        layers += [nn.Conv1d(pre_channel, w, kernel_size=1, bias=False), nn.BatchNorm1d(w), nn.ReLU()]
+        pre_channel = w
+        if dp_after(k):
+            layers.append(nn.Identity())
+    return layers, pre_channel
+
+
+class PVRCNNHead(RoIHeadBase):
+    def __init__(self, input_channels, model_cfg, num_class=1, fused=None, **kwargs):
+        model_cfg = copy.deepcopy(model_cfg)  # the reference prepends the input channels to cfg["mlps"] in place
+        super().__init__(num_class=num_class, model_cfg=model_cfg)
+        fused = FUSED_SA_DEFAULT if fused is None else bool(fused)
+        self.roi_grid_pool_layer, c_out = build_local_aggregation_module(
+            input_channels=input_channels, config=model_cfg["roi_grid_pool"], fused=fused)
+        grid = int(model_cfg["roi_grid_pool"]["grid_size"])
+        self.pre_channel = grid ** 3 * c_out
+        dp, n_shared = model_cfg["dp_ratio"], len(model_cfg["shared_fc"])
+        layers, pre = _conv_fc_stack(self.pre_channel, model_cfg["shared_fc"], lambda k: k != n_shared - 1 and dp > 0)
+        self.shared_fc_layer = nn.Sequential(*layers)
+        self.cls_layers = self.make_fc_layers(pre, self.num_class, model_cfg["cls_fc"])
+        self.reg_layers = self.make_fc_layers(pre, self.box_coder.code_size * self.num_class, model_cfg["reg_fc"])
+        self.init_weights()
+
+    def make_fc_layers(self, input_channels, output_channels, fc_list):
+        """roi_head_base.py:51-68: the Dropout sits behind the first block (dp_ratio >= 0)."""
+        layers, pre = _conv_fc_stack(input_channels, fc_list, lambda k: self.model_cfg["dp_ratio"] >= 0 and k == 0)
+        layers.append(nn.Conv1d(pre, output_channels, kernel_size=1, bias=True))
+        return nn.Sequential(*layers)
+
+    def init_weights(self):
+        for m in self.modules():
+            if isinstance(m, (nn.Conv1d, nn.Conv2d)):
+                nn.init.xavier_normal_(m.weight)
+                if m.bias is not None:
+                    nn.init.zeros_(m.bias)
+            elif isinstance(m, nn.BatchNorm1d):
+                nn.init.ones_(m.weight)
+                nn.init.zeros_(m.bias)
+        nn.init.normal_(self.reg_layers[-1].weight, mean=0.0, std=0.001)
+
+    def roi_grid_pool(self, batch_dict):
+        """-> pooled features [B * R, G^3, C]: the keypoint features weighted by their foreground scores, pooled at the
+        RoIs' grid points."""
+        from .pv_rcnn import batch_counts
+
+        batch_size = int(batch_dict["batch_size"])
+        rois = batch_dict["rois"]
+        point_coords = batch_dict["point_coords"]
+        point_features = batch_dict["point_features"] * batch_dict["point_cls_scores"].reshape(-1, 1)
+        grid = int(self.model_cfg["roi_grid_pool"]["grid_size"])
+        new_xyz = self.get_global_grid_points_of_roi(rois, grid_size=grid).reshape(-1, 3)
+        new_cnt = torch.full((batch_size,), int(rois.shape[1]) * grid ** 3, dtype=torch.int32, device=rois.device)
+        _, pooled = self.roi_grid_pool_layer(
+            xyz=point_coords[:, 1:4].contiguous(), xyz_batch_cnt=batch_counts(point_coords[:, 0], batch_size),
+            new_xyz=new_xyz, new_xyz_batch_cnt=new_cnt, features=point_features.contiguous())
+        return pooled.reshape(-1, grid ** 3, int(pooled.shape[-1]))
+
+    def forward(self, batch_dict):
+        if self.training:
+            raise NotImplementedError("PVRCNNHead: inference only (targets and losses are not built)")
+        self.proposal_layer(batch_dict, nms_config=self.model_cfg["nms_config"]["test"])
+        pooled = self.roi_grid_pool(batch_dict).transpose(1, 2)  # [B * R, C, G^3]
+        shared = self.shared_fc_layer(pooled.reshape(-1, self.pre_channel, 1))
+        rcnn_cls = self.cls_layers(shared).transpose(1, 2).squeeze(1)
+        rcnn_reg = self.reg_layers(shared).transpose(1, 2).squeeze(1)
+        batch_cls_preds, batch_box_preds = self.generate_predicted_boxes(
+            batch_size=int(batch_dict["batch_size"]), rois=batch_dict["rois"], cls_preds=rcnn_cls, box_preds=rcnn_reg)
+        batch_dict["batch_cls_preds"] = batch_cls_preds
+        batch_dict["batch_box_preds"] = batch_box_preds
+        batch_dict["cls_preds_normalized"] = False
+        return batch_dict
+
+
 @torch.no_grad()
 def post_processing(batch_dict, post_process_cfg, num_class, padded=False):
     """VoxelRCNN.post_processing.  padded=False: a list of {box3d_lidar, scores, label_preds} per frame, cut to the
@@ -267,3 +360,72 @@ def voxel_rcnn_head_kitti_car(fused_pool=None):
     return VoxelRCNNHead(input_channels={"x_conv1": 16, "x_conv2": 32, "x_conv3": 64, "x_conv4": 64},
                          model_cfg=KITTI_CAR_MODEL_CFG, point_cloud_range=[0, -40, -3, 70.4, 40, 1],
                          voxel_size=[0.05, 0.05, 0.1], num_class=1, fused_pool=fused_pool)
+
+
+PV_RCNN_KITTI_RANGE = [0, -40, -3, 70.4, 40, 1]
+PV_RCNN_KITTI_VOXEL = [0.05, 0.05, 0.1]
+PV_RCNN_KITTI_POINT_ENCODER_CFG = {
+    "point_source": "raw_points", "num_keypoints": 2048, "out_channels": 128, "sample_method": "FPS",
+    "features_source": ["bev", "x_conv1", "x_conv2", "x_conv3", "x_conv4", "raw_points"],
+    "sa_layer": {
+        "raw_points": {"mlps": [[16, 16], [16, 16]], "pool_radius": [0.4, 0.8], "nsample": [16, 16]},
+        "x_conv1": {"downsample_stride": 1, "mlps": [[16, 16], [16, 16]], "pool_radius": [0.4, 0.8],
+                    "nsample": [16, 16]},
+        "x_conv2": {"downsample_stride": 2, "mlps": [[32, 32], [32, 32]], "pool_radius": [0.8, 1.2],
+                    "nsample": [16, 32]},
+        "x_conv3": {"downsample_stride": 4, "mlps": [[64, 64], [64, 64]], "pool_radius": [1.2, 2.4],
+                    "nsample": [16, 32]},
+        "x_conv4": {"downsample_stride": 8, "mlps": [[64, 64], [64, 64]], "pool_radius": [2.4, 4.8],
+                    "nsample": [16, 32]}}}
+PV_RCNN_KITTI_POINT_HEAD_CFG = {"cls_fc": [256, 256], "class_agnostic": True, "use_point_features_before_fusion": True}
+PV_RCNN_KITTI_ROI_HEAD_CFG = {
+    "class_agnostic": True, "shared_fc": [256, 256], "cls_fc": [256, 256], "reg_fc": [256, 256], "dp_ratio": 0.3,
+    "nms_config": {
+        "train": {"nms_type": "nms_gpu", "multi_class_nms": False, "nms_pre_maxsize": 9000, "nms_post_maxsize": 512,
+                  "nms_thresh": 0.8},
+        "test": {"nms_type": "nms_gpu", "multi_class_nms": False, "nms_pre_maxsize": 1024, "nms_post_maxsize": 100,
+                 "nms_thresh": 0.7}},
+    "roi_grid_pool": {"grid_size": 6, "mlps": [[64, 64], [64, 64]], "pool_radius": [0.8, 1.6], "nsample": [16, 16],
+                      "pool_method": "max_pool"},
+    "target_config": {"box_coder": "ResidualCoder"},
+}
+PV_RCNN_KITTI_POST_PROCESS_CFG = {"score_thresh": 0.1, "output_raw_score": False,
+                                  "nms_config": {"multi_classes_nms": False, "nms_type": "nms_gpu", "nms_thresh": 0.1,
+                                                 "nms_pre_maxsize": 4096, "nms_post_maxsize": 500}}
+
+
+def pv_rcnn_kitti(fused=None):
+    """The second stage of configs/pv_rcnn/pv_rcnn_005voxel_kitti.yml (3 classes, a class-agnostic RoI head)."""
+    from .pv_rcnn import PointHeadSimple, PVRCNNSecondStage, VoxelSetAbstraction
+
+    fused = FUSED_SA_DEFAULT if fused is None else bool(fused)
+    encoder = VoxelSetAbstraction(PV_RCNN_KITTI_POINT_ENCODER_CFG, PV_RCNN_KITTI_VOXEL, PV_RCNN_KITTI_RANGE,
+                                  num_bev_features=256, num_rawpoint_features=4, fused=fused)
+    point_head = PointHeadSimple(num_class=3, input_channels=encoder.num_point_features_before_fusion,
+                                 model_cfg=PV_RCNN_KITTI_POINT_HEAD_CFG)
+    roi_head = PVRCNNHead(input_channels=encoder.num_point_features, model_cfg=PV_RCNN_KITTI_ROI_HEAD_CFG, num_class=1,
+                          fused=fused)
+    return PVRCNNSecondStage(encoder, point_head, roi_head)
+
+
+_KITTI_STAGES = {}  # device -> the pv_rcnn_kitti() that pv_rcnn_second_stage(batch_dict) runs
+
+
+@torch.no_grad()
+def pv_rcnn_second_stage(batch_dict, model=None):
+    """VoxelSetAbstraction -> PointHeadSimple -> PVRCNNHead on batch_dict (points, the per-frame point counts,
+    spatial_features, spatial_features_stride, multi_scale_3d_features, batch_box_preds, batch_cls_preds), without
+    gradients.  model: a PVRCNNSecondStage in eval mode; None runs the KITTI configuration's, pv_rcnn_kitti(), which
+    is built once per device at the first call and kept (pv_rcnn_kitti_stage(device) returns it, to load a checkpoint
+    into it)."""
+    if model is None:
+        model = pv_rcnn_kitti_stage(batch_dict["points"].device)
+    return model(batch_dict)
+
+
+def pv_rcnn_kitti_stage(device):
+    """The pv_rcnn_kitti() that pv_rcnn_second_stage(batch_dict) runs on `device`, in eval mode."""
+    device = torch.device(device)
+    if device not in _KITTI_STAGES:
+        _KITTI_STAGES[device] = pv_rcnn_kitti().to(device).eval()
+    return _KITTI_STAGES[device]
