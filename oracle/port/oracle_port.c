@@ -169,33 +169,44 @@ static void corners(const float *box, v2 *out /*[5]*/) {
   out[4] = out[0]; /* :162-163 */
 }
 
-float port_box_overlap(const float *a, const float *b) { /* box_overlap :134-229 */
-  v2 ca[5], cb[5], poly[24]; /* reference uses 16; 24 only guards the degenerate overflow */
+/* The vertex list of box_overlap before it is sorted (:134-198): the edge crossings in (i, j) order, then the admitted
+ * corners, b's before a's; returns their number and leaves their sum in *ctr.  The one polygon build behind both the
+ * area (port_box_overlap) and the vertex count (port_overlap_vertex_count). */
+#define POLY_CAP 24 /* 16 crossings + 8 corners at the most; the reference's array holds 16 */
+static int overlap_polygon(const float *a, const float *b, v2 *poly /*[POLY_CAP]*/, v2 *ctr) {
+  v2 ca[5], cb[5];
   corners(a, ca);
   corners(b, cb);
   /* NB: the reference rotates a and b corner k alternately; the values do not depend on that order */
   int cnt = 0;
-  v2 ctr = {0.f, 0.f};
+  ctr->x = 0.f;
+  ctr->y = 0.f;
   for (int i = 0; i < 4; ++i)
     for (int j = 0; j < 4; ++j) { /* :170-181 */
       if (seg_hit(ca[i + 1], ca[i], cb[j + 1], cb[j], &poly[cnt])) {
-        ctr.x = ctr.x + poly[cnt].x;
-        ctr.y = ctr.y + poly[cnt].y;
+        ctr->x = ctr->x + poly[cnt].x;
+        ctr->y = ctr->y + poly[cnt].y;
         ++cnt;
       }
     }
   for (int k = 0; k < 4; ++k) { /* :184-195 */
     if (inside(a, cb[k])) {
-      ctr.x = ctr.x + cb[k].x;
-      ctr.y = ctr.y + cb[k].y;
+      ctr->x = ctr->x + cb[k].x;
+      ctr->y = ctr->y + cb[k].y;
       poly[cnt++] = cb[k];
     }
     if (inside(b, ca[k])) {
-      ctr.x = ctr.x + ca[k].x;
-      ctr.y = ctr.y + ca[k].y;
+      ctr->x = ctr->x + ca[k].x;
+      ctr->y = ctr->y + ca[k].y;
       poly[cnt++] = ca[k];
     }
   }
+  return cnt;
+}
+
+float port_box_overlap(const float *a, const float *b) { /* box_overlap :134-229 */
+  v2 poly[POLY_CAP], ctr;
+  const int cnt = overlap_polygon(a, b, poly, &ctr);
   ctr.x /= cnt; /* :197-198 (0/0 -> NaN when cnt==0; unused then) */
   ctr.y /= cnt;
   /* bubble sort by centroid angle, point_cmp :129-132, loop :201-210 */
@@ -215,6 +226,13 @@ float port_box_overlap(const float *a, const float *b) { /* box_overlap :134-229
     area += u.x * w.y - u.y * w.x;
   }
   return (float)(fabsf(area) / 2.0); /* :219 */
+}
+
+/* how many vertices box_overlap collects for the pair (the reference keeps no such number: beyond 16 it writes past
+ * `cross_points[16]`, so a test vector is only comparable with it where this stays <= 16) */
+int port_overlap_vertex_count(const float *a, const float *b) {
+  v2 poly[POLY_CAP], ctr;
+  return overlap_polygon(a, b, poly, &ctr);
 }
 
 float port_iou_bev(const float *a, const float *b) { /* iou_bev :222-229 */
@@ -241,6 +259,11 @@ void port_boxes_iou_bev(const float *a, int na, const float *b, int nb, float *o
 void port_boxes_overlap_bev(const float *a, int na, const float *b, int nb, float *out) {
   for (int i = 0; i < na; ++i) /* iou3d_nms_kernel.cu:275-290 */
     for (int j = 0; j < nb; ++j) out[(size_t)i * nb + j] = port_box_overlap(a + i * 7, b + j * 7);
+}
+
+void port_overlap_vertices(const float *a, int na, const float *b, int nb, int32_t *out) {
+  for (int i = 0; i < na; ++i)
+    for (int j = 0; j < nb; ++j) out[(size_t)i * nb + j] = port_overlap_vertex_count(a + i * 7, b + j * 7);
 }
 
 /* Greedy NMS = suppression bits of nms_kernel (iou3d_nms_kernel.cu:310-363: bit (i,j) for j>i when

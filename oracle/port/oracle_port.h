@@ -22,6 +22,9 @@ float port_iou_bev(const float *a, const float *b);
 float port_iou_normal(const float *a, const float *b);
 void port_boxes_iou_bev(const float *a, int na, const float *b, int nb, float *out);
 void port_boxes_overlap_bev(const float *a, int na, const float *b, int nb, float *out);
+/* vertices box_overlap collects per pair, before the sort (test vectors only: the reference has no such entry) */
+int port_overlap_vertex_count(const float *a, const float *b);
+void port_overlap_vertices(const float *a, int na, const float *b, int nb, int32_t *out);
 void port_nms(const float *boxes, int n, float thresh, int normal, int32_t *keep, int32_t *num);
 
 void port_pillar_scatter(const float *feats, const int32_t *coords, int64_t m, int c, int batch,

@@ -100,6 +100,15 @@ def boxes_overlap_bev(a, b, kind="port"):
     return out
 
 
+def overlap_vertices(a, b):
+    """int32 [na, nb]: how many vertices the port's box_overlap collects for each pair (crossings + admitted corners,
+    before the sort).  Port only: above 16 the reference writes past its array, so there is nothing to compare."""
+    a, b = _c(a, _f), _c(b, _f)
+    out = np.empty((len(a), len(b)), _i)
+    _lib("port").port_overlap_vertices(_p(a), C.c_int(len(a)), _p(b), C.c_int(len(b)), _p(out))
+    return out
+
+
 def libm_eval(op, x, y=None):
     """The host libm's sinf / cosf / expf / atanf / atan2f (op 0..4) over float32 arrays."""
     x = _c(x, _f)

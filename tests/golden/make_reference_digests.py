@@ -20,6 +20,7 @@ TESTS = [
     "tests/test_oracle.py::test_voxelize_port_equals_reference",
     "tests/test_oracle.py::test_iou_nms_port_equals_reference",
     "tests/test_oracle.py::test_iou_degenerate_pairs",
+    "tests/test_oracle.py::test_iou_nms_port_equals_reference_on_box_families",
     "tests/test_oracle.py::test_decode_port_equals_reference",
     "tests/test_oracle.py::test_bev_pool_port_equals_reference",
     "tests/test_oracle.py::test_hard_voxelize_float64_port_equals_ref",
