@@ -1130,6 +1130,48 @@ int pd3_ssd_postprocess(const float *head_map, int64_t batch_stride, int cls_cha
                         float *out_scores, int64_t *out_labels, int32_t *out_count, void *workspace,
                         size_t workspace_bytes, void *stream, int selection);
 
+/* ---------------------------------------------------------------------------------------------
+ * CaDDN's frustum-to-voxel and map-to-BEV stage (csrc/caddn.hip; models/detection/caddn: ffe/ffe.py:75-97,
+ * f2v/frustum_grid_generator.py:87-154, f2v/sampler.py, f2v/frustum_to_voxel.py, caddn.py:113-122).  Common arguments:
+ *   image_features [batch, channels, h, w] fp32 (after channel_reduce), depth_logits [batch, num_bins + 1, h, w] fp32,
+ *   lidar_to_cam [batch, 4, 4], cam_to_img [batch, 3, 4] fp32 and image_shape [batch, 2] int32 (H, W of the full-resolution
+ *   image; the grid is normalised by the maximum over the batch), all on the device; pc_min[3], voxel_size[3] host floats;
+ *   the voxel grid (grid_x, grid_y, grid_z); mode 0 UD / 1 LID / 2 SID with depth_min, depth_max (utils/depth.py:38-47).
+ * The arithmetic order of every step is stated at the top of csrc/caddn.hip and restated in tests/golden/caddn_numpy.py.
+ * No atomics, no host synchronisation.  PD3_EINVAL for a size below 1 or an unknown mode, PD3_EWORKSPACE, PD3_EUNSUPPORTED
+ * for batch > 65535, grid_x * grid_y or h * w * max(channels, num_bins + 1) above 2^31 - 1.
+ *
+ * frustum_grid: grid [batch, grid_x, grid_y, grid_z, 3] fp32, FrustumGridGenerator.forward's normalised sampling grid (voxel
+ *   centres index + 0.5; scale = |w| > 1e-8 ? 1 / (w + 1e-8) : 1 after the 4x4 product and after the projection; a
+ *   non-finite component is -2).
+ * frustum_to_voxel: voxel_features [batch, channels, grid_z, grid_y, grid_x] fp32, FrustumToVoxel.forward over
+ *   FFE.create_frustum_features without the frustum volume or the grid in memory (any channels >= 1): a pack step writes
+ *   softmax(depth_logits)[:, :-1] and the features pixel-major into the workspace, then a thread per voxel writes
+ *   sum_{4 (y, x) corners} w_xy * f[c, y, x] * (sum_{2 z corners} w_z * p[z, y, x]), zero padding per corner, zeros included.
+ * frustum_to_bev: bev [batch, c_out, grid_y, grid_x] = relu(scale[o] * sum_k weight[o, k] * voxel[k] + shift[o]) with
+ *   k = c * grid_z + z (the reference's flatten(1, 2)), weight [c_out, channels * grid_z], scale / shift [c_out] the folded
+ *   BatchNorm: map_to_bev on the fp32 matrix cores in the same kernel, the voxel volume never in memory.  The sum is one
+ *   fp32 fmaf chain from 0, z ascending and within a z the channels in the order stated in csrc/caddn.hip; a column's result depends neither on its tile, the
+ *   launch nor its frame's place in the batch; a column without a sample is relu(shift).  channels and c_out multiples of
+ *   16 up to 64 and grid_z <= 32, PD3_EUNSUPPORTED otherwise (the caller composes frustum_to_voxel with a convolution).
+ */
+int pd3_frustum_grid(const float *lidar_to_cam, const float *cam_to_img, const int32_t *image_shape, int batch,
+                     int grid_x, int grid_y, int grid_z, const float *pc_min, const float *voxel_size, int mode,
+                     double depth_min, double depth_max, int num_bins, float *grid, void *stream);
+size_t pd3_frustum_to_voxel_workspace(int batch, int channels, int num_bins, int h, int w);
+int pd3_frustum_to_voxel(const float *image_features, const float *depth_logits, const float *lidar_to_cam,
+                         const float *cam_to_img, const int32_t *image_shape, int batch, int channels, int num_bins,
+                         int h, int w, int grid_x, int grid_y, int grid_z, const float *pc_min,
+                         const float *voxel_size, int mode, double depth_min, double depth_max, float *voxel_features,
+                         void *workspace, size_t workspace_bytes, void *stream);
+size_t pd3_frustum_to_bev_workspace(int batch, int channels, int num_bins, int h, int w, int grid_z, int c_out);
+int pd3_frustum_to_bev(const float *image_features, const float *depth_logits, const float *lidar_to_cam,
+                       const float *cam_to_img, const int32_t *image_shape, int batch, int channels, int num_bins,
+                       int h, int w, int grid_x, int grid_y, int grid_z, const float *pc_min, const float *voxel_size,
+                       int mode, double depth_min, double depth_max, const float *weight, const float *scale,
+                       const float *shift, int c_out, float *bev, void *workspace, size_t workspace_bytes,
+                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif

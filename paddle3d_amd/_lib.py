@@ -268,6 +268,21 @@ _SIGNATURES_PVRCNN = {
 
 SYMBOLS_PVRCNN = tuple(_SIGNATURES_PVRCNN)
 
+# CaDDN's frustum-to-voxel and map-to-BEV stage (csrc/caddn.hip).  The fourth table of this kind, for the same reason:
+# its guarded scenarios and the completeness assertion over SYMBOLS_CADDN are in tests/test_memory_safety_caddn_gpu.py.
+_CADDN_GRID = [C.c_int] * 3 + [C.c_void_p] * 2 + [C.c_int, C.c_double, C.c_double]  # grid, pc_min, voxel_size, mode, depths
+_CADDN_IN = [C.c_void_p] * 5 + [C.c_int] * 5 + _CADDN_GRID  # features, logits, calibration, image_shape, B, C, D, h, w
+_SIGNATURES_CADDN = {
+    "pd3_frustum_grid": (C.c_int, [C.c_void_p] * 3 + [C.c_int] + _CADDN_GRID + [C.c_int] + [C.c_void_p] * 2),
+    "pd3_frustum_to_voxel_workspace": (C.c_size_t, [C.c_int] * 5),
+    "pd3_frustum_to_voxel": (C.c_int, _CADDN_IN + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pd3_frustum_to_bev_workspace": (C.c_size_t, [C.c_int] * 7),
+    "pd3_frustum_to_bev": (C.c_int, _CADDN_IN + [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                                    C.c_void_p]),
+}
+
+SYMBOLS_CADDN = tuple(_SIGNATURES_CADDN)
+
 
 class Paddle3DAmdError(RuntimeError):
     pass
@@ -281,7 +296,8 @@ def lib() -> C.CDLL:
             "(there is no CPU / PyTorch fallback for the HIP ops)")
     handle = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(_SIGNATURES.items()) + list(_SIGNATURES_ROI.items()) +
-                              list(_SIGNATURES_HEAD.items()) + list(_SIGNATURES_PVRCNN.items())):
+                              list(_SIGNATURES_HEAD.items()) + list(_SIGNATURES_PVRCNN.items()) +
+                              list(_SIGNATURES_CADDN.items())):
         try:
             fn = getattr(handle, name)
         except AttributeError as e:  # pragma: no cover
