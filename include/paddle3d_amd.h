@@ -1131,6 +1131,40 @@ int pd3_ssd_postprocess(const float *head_map, int64_t batch_stride, int cls_cha
                         size_t workspace_bytes, void *stream, int selection);
 
 /* ---------------------------------------------------------------------------------------------
+ * BEVFormer's encoder attention (csrc/bevformer.hip; models/transformers/encoders.py:120-176 point_sampling,
+ * attentions/spatial_cross_attention.py:81-212 and :310-428, attentions/temporal_self_attention.py:207-272), fp32.  The
+ * arithmetic order of every output is in the header of csrc/bevformer.hip; tests/golden/bevformer_numpy.py restates it.
+ * value is the projected value [rows, spatial_size, num_heads, channels]; spatial_shapes [num_levels, 2] (H, W) and
+ * level_start_index [num_levels] are int64 on the device.  Statuses: 0, PD3_EINVAL (-1), PD3_EUNSUPPORTED (-3) for a
+ * shape outside: channels % 4 == 0 with value and out 16-byte aligned, num_levels * num_point <= 32, num_cams <= 8,
+ * num_point % num_anchors == 0 (nothing is launched then), or a positive hipError_t.
+ *
+ * pd3_bevformer_point_sampling: ref_3d [num_anchors, num_query, 3] in [0, 1], lidar2img [batch, num_cams, 4, 4],
+ *   pc_range[6] host floats, the image size all frames are normalised by -> reference_points_cam [num_cams, batch,
+ *   num_query, num_anchors, 2], bev_mask [num_cams, batch, num_query, num_anchors] uint8, hit_bits [batch, num_query]
+ *   uint8 (bit c: camera c sees an anchor of the query) and hit_count [batch, num_query] uint8.
+ * pd3_bevformer_sca: value rows batch * num_cams (row b * num_cams + c), sampling_offsets [batch, num_query, num_heads,
+ *   num_levels, num_point, 2] and attention_logits [batch, num_query, num_heads, num_levels * num_point] as the two
+ *   Linear layers give them on the BEV queries -> out [batch, num_query, num_heads * channels]: the softmax, the
+ *   sampling of every camera whose hit bit is set (summed in camera order) and the division by max(hit count, 1).
+ * pd3_bevformer_tsa: value rows batch * 2 (row 2 b + j for queue entry j), sampling_offsets [batch, num_query,
+ *   num_heads, 2, num_levels, num_point, 2], attention_logits [batch, num_query, num_heads, 2, num_levels * num_point],
+ *   reference_points [batch * 2, num_query, num_levels, 2] -> out [batch, num_query, num_heads * channels], the mean of
+ *   the two queue entries' samples.
+ * ------------------------------------------------------------------------------------------- */
+int pd3_bevformer_point_sampling(const void *ref_3d, const void *lidar2img, const float *pc_range, int img_h, int img_w,
+                                 int batch, int num_cams, int num_query, int num_anchors, void *reference_points_cam,
+                                 void *bev_mask, void *hit_bits, void *hit_count, void *stream);
+int pd3_bevformer_sca(const void *value, const int64_t *spatial_shapes, const int64_t *level_start_index,
+                      const void *sampling_offsets, const void *attention_logits, const void *reference_points_cam,
+                      const void *hit_bits, int batch, int num_cams, int spatial_size, int num_heads, int channels,
+                      int num_levels, int num_query, int num_point, int num_anchors, void *out, void *stream);
+int pd3_bevformer_tsa(const void *value, const int64_t *spatial_shapes, const int64_t *level_start_index,
+                      const void *sampling_offsets, const void *attention_logits, const void *reference_points,
+                      int batch, int spatial_size, int num_heads, int channels, int num_levels, int num_query,
+                      int num_point, void *out, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * CaDDN's frustum-to-voxel and map-to-BEV stage (csrc/caddn.hip; models/detection/caddn: ffe/ffe.py:75-97,
  * f2v/frustum_grid_generator.py:87-154, f2v/sampler.py, f2v/frustum_to_voxel.py, caddn.py:113-122).  Common arguments:
  *   image_features [batch, channels, h, w] fp32 (after channel_reduce), depth_logits [batch, num_bins + 1, h, w] fp32,

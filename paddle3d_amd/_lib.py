@@ -283,6 +283,16 @@ _SIGNATURES_CADDN = {
 
 SYMBOLS_CADDN = tuple(_SIGNATURES_CADDN)
 
+# BEVFormer's encoder attention (csrc/bevformer.hip).  The fifth table of this kind, for the same reason: its guarded
+# scenarios and the completeness assertion over SYMBOLS_BEVFORMER are in tests/test_memory_safety_bevformer_gpu.py.
+_SIGNATURES_BEVFORMER = {
+    "pd3_bevformer_point_sampling": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_void_p] * 5),
+    "pd3_bevformer_sca": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 9 + [C.c_void_p] * 2),
+    "pd3_bevformer_tsa": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 7 + [C.c_void_p] * 2),
+}
+
+SYMBOLS_BEVFORMER = tuple(_SIGNATURES_BEVFORMER)
+
 
 class Paddle3DAmdError(RuntimeError):
     pass
@@ -297,7 +307,7 @@ def lib() -> C.CDLL:
     handle = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(_SIGNATURES.items()) + list(_SIGNATURES_ROI.items()) +
                               list(_SIGNATURES_HEAD.items()) + list(_SIGNATURES_PVRCNN.items()) +
-                              list(_SIGNATURES_CADDN.items())):
+                              list(_SIGNATURES_CADDN.items()) + list(_SIGNATURES_BEVFORMER.items())):
         try:
             fn = getattr(handle, name)
         except AttributeError as e:  # pragma: no cover
