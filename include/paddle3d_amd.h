@@ -1131,6 +1131,45 @@ int pd3_ssd_postprocess(const float *head_map, int64_t batch_stride, int cls_cha
                         size_t workspace_bytes, void *stream, int selection);
 
 /* ---------------------------------------------------------------------------------------------
+ * BEVFormer's decoder, head and NMS-free decode (csrc/bevformer_decoder.hip; models/transformers/decoders.py,
+ * decoder_layers.py, attentions/multihead_attention.py, attentions/spatial_cross_attention.py:531-640,
+ * utils/box_coder.py:133-214, utils/box.py:107-138), fp32, inference only, on `stream`, no host synchronisation, no
+ * atomics on global memory, every output element written on every call.  The arithmetic order of every output is in
+ * the header of csrc/bevformer_decoder.hip; tests/golden/bevformer_decoder_numpy.py restates it.  Statuses: 0,
+ * PD3_EINVAL (-1), PD3_EUNSUPPORTED (-3, nothing is launched), or a positive hipError_t.
+ *
+ * pd3_mha_forward: paddle.nn.MultiHeadAttention's core without masks or dropout.  q [batch, num_query, num_heads,
+ *   head_dim], k and v [batch, num_key, num_heads, head_dim] (the Linear outputs viewed per head), scale = head_dim **
+ *   -0.5 -> out [batch, num_query, num_heads * head_dim] = softmax((q * scale) k^T) v per head, an exact two-pass
+ *   softmax whose bits depend neither on the tiling nor on the frame's place in the batch.  PD3_EUNSUPPORTED unless
+ *   head_dim % 16 == 0, head_dim <= 128, num_key <= 2048 and q, k, v, out are 16-byte aligned; num_key < 1 is
+ *   PD3_EINVAL; batch == 0 or num_query == 0 is success without a launch.
+ * pd3_bevformer_dec_ca: CustomMSDeformableAttention's sampling.  value [batch, spatial_size, num_heads, channels]
+ *   (projected), sampling_offsets [batch, num_query, num_heads, num_levels, num_point, 2] and attention_logits [batch,
+ *   num_query, num_heads, num_levels * num_point] as the two Linear layers give them, reference_points [batch,
+ *   num_query, num_ref_levels, 2] with num_ref_levels 1 (broadcast over the levels) or num_levels, spatial_shapes
+ *   [num_levels, 2] (H, W) and level_start_index [num_levels] int64 on the device -> out [batch, num_query, num_heads *
+ *   channels].  PD3_EUNSUPPORTED unless channels % 4 == 0 with value and out 16-byte aligned and num_levels * num_point
+ *   <= 32.
+ * pd3_nms_free_decode: NMSFreeCoder.decode for the whole batch.  cls_scores [batch, num_query, num_classes] logits,
+ *   bbox_preds [batch, num_query, code_size] (code_size 8 or 10; centres in metres), post_center_range[6] host floats,
+ *   score_threshold (negative: None), bottom_center != 0: z = z - h * 0.5f on the kept rows -> boxes [batch, max_num,
+ *   code_size - 1] (cx, cy, cz, w, l, h, rot[, vx, vy]), scores [batch, max_num], labels [batch, max_num] int32 and
+ *   count [batch] int32: the kept rows of the max_num best (score descending, flat index ascending; a NaN score is
+ *   never kept) in rank order, rows at and after count zeros with label -1.  max_num > num_query * num_classes or a
+ *   score_threshold that is no finite number is PD3_EINVAL, max_num > 1024 PD3_EUNSUPPORTED.
+ * ------------------------------------------------------------------------------------------- */
+int pd3_mha_forward(const void *q, const void *k, const void *v, int batch, int num_query, int num_key, int num_heads,
+                    int head_dim, float scale, void *out, void *stream);
+int pd3_bevformer_dec_ca(const void *value, const int64_t *spatial_shapes, const int64_t *level_start_index,
+                         const void *sampling_offsets, const void *attention_logits, const void *reference_points,
+                         int batch, int spatial_size, int num_heads, int channels, int num_levels, int num_query,
+                         int num_point, int num_ref_levels, void *out, void *stream);
+int pd3_nms_free_decode(const void *cls_scores, const void *bbox_preds, const float *post_center_range, int batch,
+                        int num_query, int num_classes, int code_size, int max_num, double score_threshold,
+                        int bottom_center, void *boxes, void *scores, void *labels, void *count, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * BEVFormer's encoder attention (csrc/bevformer.hip; models/transformers/encoders.py:120-176 point_sampling,
  * attentions/spatial_cross_attention.py:81-212 and :310-428, attentions/temporal_self_attention.py:207-272), fp32.  The
  * arithmetic order of every output is in the header of csrc/bevformer.hip; tests/golden/bevformer_numpy.py restates it.

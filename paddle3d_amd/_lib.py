@@ -293,6 +293,17 @@ _SIGNATURES_BEVFORMER = {
 
 SYMBOLS_BEVFORMER = tuple(_SIGNATURES_BEVFORMER)
 
+# BEVFormer's decoder, head and NMS-free decode (csrc/bevformer_decoder.hip).  The sixth table of this kind, for the same
+# reason: its guarded scenarios and the completeness assertion over SYMBOLS_BEVFORMER_DEC are in
+# tests/test_memory_safety_bevformer_dec_gpu.py.
+_SIGNATURES_BEVFORMER_DEC = {
+    "pd3_mha_forward": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_float] + [C.c_void_p] * 2),
+    "pd3_bevformer_dec_ca": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 8 + [C.c_void_p] * 2),
+    "pd3_nms_free_decode": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_double, C.c_int] + [C.c_void_p] * 5),
+}
+
+SYMBOLS_BEVFORMER_DEC = tuple(_SIGNATURES_BEVFORMER_DEC)
+
 
 class Paddle3DAmdError(RuntimeError):
     pass
@@ -307,7 +318,8 @@ def lib() -> C.CDLL:
     handle = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(_SIGNATURES.items()) + list(_SIGNATURES_ROI.items()) +
                               list(_SIGNATURES_HEAD.items()) + list(_SIGNATURES_PVRCNN.items()) +
-                              list(_SIGNATURES_CADDN.items()) + list(_SIGNATURES_BEVFORMER.items())):
+                              list(_SIGNATURES_CADDN.items()) + list(_SIGNATURES_BEVFORMER.items()) +
+                              list(_SIGNATURES_BEVFORMER_DEC.items())):
         try:
             fn = getattr(handle, name)
         except AttributeError as e:  # pragma: no cover

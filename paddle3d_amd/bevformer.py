@@ -34,7 +34,8 @@ Where this departs from the reference, on purpose:
 `ref_2d += shift` is reproduced as the reference keeps it: both queue entries get the shifted points.
 
 Linear, LayerNorm and the FFN are torch.  Inference only; with device tensors in img_metas nothing in the forwards
-synchronises with the host.  The decoder and PerceptionTransformer's can-bus handling are not part of this module.
+synchronises with the host.  The decoder, the detection head and the NMS-free decode are in paddle3d_amd/bevformer_head.py;
+PerceptionTransformer's can-bus handling is not implemented.
 """
 from __future__ import annotations
 

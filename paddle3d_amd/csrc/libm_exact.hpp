@@ -221,6 +221,21 @@ PD3_HD float expf(float x) {
   return expf_main(x, [](int i) { return exp2f_tab(i); });
 }
 
+// expf with the table read through `tab` (see expf_main), for a caller that keeps the 32 entries in LDS: exp2f_tab's
+// array lives in memory, and a read of it per call is a global load the polynomial waits for.
+template <class Tab>
+PD3_HD float expf_with(float x, Tab tab) {
+  if (expf_is_special(x)) {
+    const uint32_t abstop = (f2u(x) >> 20) & 0x7ffu;
+    if (f2u(x) == 0xff800000u) return 0.0f;
+    if (abstop >= 0x7f8u) return x + x;
+    if (x > 0x1.62e42ep6f) return u2f(0x7f800000u);  // overflow
+    if (x < -0x1.9fe368p6f) return 0.0f;             // underflow
+    if (x < -0x1.9d1d9ep6f) return u2f(1u);          // __math_may_uflowf: 0x1.4p-75f * 0x1.4p-75f
+  }
+  return expf_main(x, tab);
+}
+
 // ---- atanf / atan2f (fdlibm) ------------------------------------------------------------------------------
 PD3_HD float atanf(float x) {
   const float atanhi[4] = {u2f(0x3eed6338u), u2f(0x3f490fdau), u2f(0x3f7b985eu), u2f(0x3fc90fdau)};
