@@ -1131,6 +1131,39 @@ int pd3_ssd_postprocess(const float *head_map, int64_t batch_stride, int cls_cha
                         size_t workspace_bytes, void *stream, int selection);
 
 /* ---------------------------------------------------------------------------------------------
+ * PETR / PETRv2's head (csrc/petr.hip; models/heads/dense_heads/petr_head.py:364-450, models/layers/petr_transformer.py:
+ * 277-360), fp32, inference only, on `stream`, no host synchronisation, no atomics on global memory, every output
+ * element written on every call.  The arithmetic order of every output is in the header of csrc/petr.hip;
+ * tests/golden/petr_numpy.py restates it.  Statuses: 0, PD3_EINVAL (-1), PD3_EUNSUPPORTED (-3, nothing is launched), or
+ * a positive hipError_t.
+ *
+ * pd3_mha_stream_forward: paddle.nn.MultiHeadAttention's core for any number of keys, with an optional key padding
+ *   mask.  q [batch, num_query, num_heads, head_dim], k and v [batch, num_key, num_heads, head_dim] (the Linear outputs
+ *   viewed per head), key_mask uint8 [batch, num_key] or NULL (non-zero: padded; the fp32 value -1e9f is added to the
+ *   key's score, as Paddle's converted boolean attn_mask does -- the key is not skipped), scale = head_dim ** -0.5 ->
+ *   out [batch, num_query, num_heads * head_dim] = softmax((q * scale) k^T + mask) v per head: an exact two-pass
+ *   softmax that keeps no score row anywhere (LDS use does not depend on num_key) and whose bits depend on (num_key,
+ *   head_dim) only, not on num_query, the tiling, the frame's place in the batch or the stream.  The bits are not those
+ *   of pd3_mha_forward.  PD3_EUNSUPPORTED unless head_dim % 16 == 0, head_dim <= 128 and q, k, v, out are 16-byte
+ *   aligned (the kernel loads and stores single floats today: the alignment is reserved for vector loads); num_key < 1
+ *   is PD3_EINVAL; batch == 0 or num_query == 0 is success without a launch.
+ * pd3_petr_coords3d: PETRHead.position_embeding from the frustum grid through inverse_sigmoid in one launch.
+ *   img2lidars [num_views, 4, 4] (num_views = batch * cameras), the feature map's feat_h x feat_w, depth_num bins from
+ *   depth_start (lid != 0: linear-increasing, else uniform) up to position_range[3], pad_h x pad_w the padded image,
+ *   position_range[6] host floats, token_mask uint8 [num_views, feat_h, feat_w] or NULL -> coords [num_views, 3 *
+ *   depth_num, feat_h, feat_w] (channel d * 3 + c; the logarithm is (float)log((double)ratio)) and, unless NULL,
+ *   coords_mask uint8 [num_views, feat_h, feat_w]: more than depth_num * 0.5 of the token's 3 * depth_num normalised
+ *   coordinates outside [0, 1], OR-ed with token_mask.  A zero num_views, feat_h, feat_w or depth_num is success
+ *   without a launch; no alignment is needed; PD3_EUNSUPPORTED only when num_views * feat_h * ceil(feat_w / 64)
+ *   exceeds 2^31 - 1.
+ * ------------------------------------------------------------------------------------------- */
+int pd3_mha_stream_forward(const void *q, const void *k, const void *v, const void *key_mask, int batch, int num_query,
+                           int num_key, int num_heads, int head_dim, float scale, void *out, void *stream);
+int pd3_petr_coords3d(const void *img2lidars, int num_views, int feat_h, int feat_w, int depth_num, int pad_h, int pad_w,
+                      double depth_start, const float *position_range, int lid, const void *token_mask, void *coords,
+                      void *coords_mask, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * BEVFormer's decoder, head and NMS-free decode (csrc/bevformer_decoder.hip; models/transformers/decoders.py,
  * decoder_layers.py, attentions/multihead_attention.py, attentions/spatial_cross_attention.py:531-640,
  * utils/box_coder.py:133-214, utils/box.py:107-138), fp32, inference only, on `stream`, no host synchronisation, no

@@ -304,6 +304,15 @@ _SIGNATURES_BEVFORMER_DEC = {
 
 SYMBOLS_BEVFORMER_DEC = tuple(_SIGNATURES_BEVFORMER_DEC)
 
+# PETR / PETRv2's head (csrc/petr.hip).  The seventh table of this kind, for the same reason: its guarded scenarios and
+# the completeness assertion over SYMBOLS_PETR are in tests/test_memory_safety_petr_gpu.py.
+_SIGNATURES_PETR = {
+    "pd3_mha_stream_forward": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_float] + [C.c_void_p] * 2),
+    "pd3_petr_coords3d": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.c_double, C.c_void_p, C.c_int] + [C.c_void_p] * 4),
+}
+
+SYMBOLS_PETR = tuple(_SIGNATURES_PETR)
+
 
 class Paddle3DAmdError(RuntimeError):
     pass
@@ -319,7 +328,7 @@ def lib() -> C.CDLL:
     for name, (res, args) in (list(_SIGNATURES.items()) + list(_SIGNATURES_ROI.items()) +
                               list(_SIGNATURES_HEAD.items()) + list(_SIGNATURES_PVRCNN.items()) +
                               list(_SIGNATURES_CADDN.items()) + list(_SIGNATURES_BEVFORMER.items()) +
-                              list(_SIGNATURES_BEVFORMER_DEC.items())):
+                              list(_SIGNATURES_BEVFORMER_DEC.items()) + list(_SIGNATURES_PETR.items())):
         try:
             fn = getattr(handle, name)
         except AttributeError as e:  # pragma: no cover
