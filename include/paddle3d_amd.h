@@ -1131,6 +1131,45 @@ int pd3_ssd_postprocess(const float *head_map, int64_t batch_stride, int cls_cha
                         size_t workspace_bytes, void *stream, int selection);
 
 /* ---------------------------------------------------------------------------------------------
+ * SqueezeSegV3 (csrc/squeezeseg.hip; models/backbones/sac.py:186-197, transforms/reader.py:287-366,
+ * transforms/normalize.py NormalizeRangeImage), fp32, inference only, on `stream`, no host synchronisation, every
+ * output element written on every call.  The arithmetic order of every output is in the header of
+ * csrc/squeezeseg.hip; tests/golden/squeezeseg_numpy.py restates it.  Statuses: 0, PD3_EINVAL (-1), PD3_EWORKSPACE
+ * (-2), PD3_EUNSUPPORTED (-3, nothing is launched), or a positive hipError_t.
+ *
+ * pd3_sac_isk_forward: SACISKBlock.forward from xyz and feature to its first MLP layer, in one launch:
+ *   Y = relu(BN(conv1x1(unfold3x3(feature) * sigmoid(BN(conv7x7(xyz)))))).  xyz [batch, 3, height, width], feature and
+ *   out [batch, channels, height, width], NCHW.  attn_weight_packed holds the [9 * channels, 3, 7, 7] weight as floats
+ *   [9 * channels / 16][37][64] and mlp_weight_packed the [channels, 9 * channels] weight as [9 * channels / 16][4]
+ *   [channels / 16][64] (the lane orders are in the kernel file's header; ops/squeezeseg.py packs them); attn_scale,
+ *   attn_shift [9 * channels] and mlp_scale, mlp_shift [channels] are the folded BatchNorms (scale = gamma / sqrt(var +
+ *   eps), shift = (bias - mean) * scale + beta; the attention convolution has a bias).  None of the three [batch, 9 *
+ *   channels, height, width] intermediates is written anywhere.  The bits of a pixel depend on `channels` only: not on
+ *   batch, height, width, the pixel's place, the grid or the stream.  No atomics.  PD3_EUNSUPPORTED unless channels %
+ *   16 == 0, 16 <= channels <= 256, height >= 1, width >= 1 and batch * height * ceil(width / 16) < 2^30; batch
+ *   == 0 is success without a launch; nothing needs an alignment.
+ * pd3_range_project: the reader's spherical projection and the image normalisation for `batch` frames in one call.
+ *   points [num_points, 4] (x, y, z, remission; the frames concatenated), offsets int32 [batch + 1] on the device,
+ *   fov_up_deg / fov_down_deg the two inclinations in degrees (3, -25), mean[5], std[5] host doubles, workspace uint64
+ *   [batch, height, width] (workspace_bytes >= 8 * batch * height * width, 8-byte aligned; filled by the call) ->
+ *   image [batch, 5, height, width] (range, x, y, z, remission; an empty pixel is -1 before the normalisation
+ *   (float)((double)(float)((double)v - mean) / std)), proj_idx int32 [batch, height, width] (index inside the frame,
+ *   -1 when empty), proj_mask uint8 = proj_idx > 0 (the reference's form: point 0's pixel is masked out too), proj_y,
+ *   proj_x int32 [num_points] (-1 for a point with a non-finite coordinate, zero depth or outside every frame; such a
+ *   point takes no pixel).  Pixel coordinates are computed in fp64 from the fp32 inputs; a pixel takes its nearest
+ *   point, the smaller index on equal depths, through a 64-bit atomicMin (exact in any order).  Three launches.
+ *   num_points up to 2^31 - 1.
+ * ------------------------------------------------------------------------------------------- */
+int pd3_sac_isk_forward(const void *xyz, const void *feature, const void *attn_weight_packed, const void *attn_scale,
+                        const void *attn_shift, const void *mlp_weight_packed, const void *mlp_scale,
+                        const void *mlp_shift, int batch, int channels, int height, int width, void *out,
+                        void *stream);
+int pd3_range_project(const void *points, int64_t num_points, const void *offsets, int batch, int height, int width,
+                      double fov_up_deg, double fov_down_deg, const double *mean, const double *std, void *image,
+                      void *proj_idx, void *proj_mask, void *proj_y, void *proj_x, void *workspace,
+                      size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * PETR / PETRv2's head (csrc/petr.hip; models/heads/dense_heads/petr_head.py:364-450, models/layers/petr_transformer.py:
  * 277-360), fp32, inference only, on `stream`, no host synchronisation, no atomics on global memory, every output
  * element written on every call.  The arithmetic order of every output is in the header of csrc/petr.hip;

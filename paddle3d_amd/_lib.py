@@ -313,6 +313,17 @@ _SIGNATURES_PETR = {
 
 SYMBOLS_PETR = tuple(_SIGNATURES_PETR)
 
+# SqueezeSegV3's SAC block and range projection (csrc/squeezeseg.hip).  The eighth table of this kind, for the same
+# reason: its guarded scenarios and the completeness assertion over SYMBOLS_SQSEG are in
+# tests/test_memory_safety_squeezeseg_gpu.py.
+_SIGNATURES_SQSEG = {
+    "pd3_sac_isk_forward": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 4 + [C.c_void_p] * 2),
+    "pd3_range_project": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p] + [C.c_int] * 3 + [C.c_double] * 2 +
+                          [C.c_void_p] * 8 + [C.c_size_t, C.c_void_p]),
+}
+
+SYMBOLS_SQSEG = tuple(_SIGNATURES_SQSEG)
+
 
 class Paddle3DAmdError(RuntimeError):
     pass
@@ -328,7 +339,8 @@ def lib() -> C.CDLL:
     for name, (res, args) in (list(_SIGNATURES.items()) + list(_SIGNATURES_ROI.items()) +
                               list(_SIGNATURES_HEAD.items()) + list(_SIGNATURES_PVRCNN.items()) +
                               list(_SIGNATURES_CADDN.items()) + list(_SIGNATURES_BEVFORMER.items()) +
-                              list(_SIGNATURES_BEVFORMER_DEC.items()) + list(_SIGNATURES_PETR.items())):
+                              list(_SIGNATURES_BEVFORMER_DEC.items()) + list(_SIGNATURES_PETR.items()) +
+                              list(_SIGNATURES_SQSEG.items())):
         try:
             fn = getattr(handle, name)
         except AttributeError as e:  # pragma: no cover
