@@ -1131,6 +1131,46 @@ int pd3_ssd_postprocess(const float *head_map, int64_t batch_stride, int cls_cha
                         size_t workspace_bytes, void *stream, int selection);
 
 /* ---------------------------------------------------------------------------------------------
+ * BEVFusion's Anchor3DHead at inference (csrc/anchor3d_head.hip; models/heads/dense_heads/anchor3d_head.py:146-161,
+ * :378-520, models/detection/bevfusion/utils.py:92-103, :189-276, utils/box_coder.py:270-310), fp32, on `stream`, no
+ * host synchronisation, every count on the device, every output element written on every call.  The arithmetic order
+ * of every output is in the header of csrc/anchor3d_head.hip; tests/golden/anchor3d_numpy.py restates it.  Statuses:
+ * 0, PD3_EINVAL (-1), PD3_EWORKSPACE (-2), PD3_EUNSUPPORTED (-3, nothing is launched), or a positive hipError_t.
+ *
+ * Common to both entry points: anchors [feat_h * feat_w * num_anchors, code_size] (anchor (y * feat_w + x) *
+ * num_anchors + a, map channel a * width + component), K = min(nms_pre, anchors) or all anchors when nms_pre <= 0,
+ * sigmoid class scores, a direction classifier; score_thr, nms_thr, dir_offset and dir_limit_offset as fp32 ->
+ * boxes [batch, max_num, code_size], scores [batch, max_num], labels int32 [batch, max_num], counts int32 [batch];
+ * rows past counts[b] are zero.  PD3_EUNSUPPORTED unless 1 <= num_classes <= 16, 1 <= num_anchors <= 32, 7 <=
+ * code_size <= 16, 1 <= K <= 1024, 1 <= max_num <= 1024 (and feat_h * feat_w * num_anchors < 2^30, batch *
+ * num_classes <= 65535); batch == 0 is success without a launch; nothing needs an alignment.
+ * pd3_anchor3d_head_workspace: bytes of workspace for either entry point (0 for a shape they refuse); needs no GPU.
+ * pd3_anchor3d_head_forward: the LAZY head.  feat [batch, channels, feat_h, feat_w]; cls_weight_packed: conv_cls's
+ *   [num_anchors * num_classes, channels] weight in the MFMA lane order of the kernel file's header
+ *   (ops/anchor3d_head.py pack_cls_weight); reg_weight [num_anchors * code_size, channels] and dir_weight
+ *   [num_anchors * 2, channels] as the convolutions hold them; the three biases.  Only conv_cls runs densely and only
+ *   the per-anchor maximum score (4 * anchors bytes per frame) is written; conv_reg, conv_dir_cls and the class
+ *   scores are evaluated at the K selected anchors.  Also PD3_EUNSUPPORTED unless channels % 16 == 0 and 16 <=
+ *   channels <= 512.
+ * pd3_anchor3d_get_bboxes: the same sequence from existing maps cls_score [batch, num_anchors * num_classes, feat_h,
+ *   feat_w], bbox_pred [batch, num_anchors * code_size, ..], dir_cls_pred [batch, num_anchors * 2, ..].
+ * ------------------------------------------------------------------------------------------- */
+size_t pd3_anchor3d_head_workspace(int batch, int feat_h, int feat_w, int num_anchors, int num_classes, int code_size,
+                                   int nms_pre);
+int pd3_anchor3d_head_forward(const void *feat, const void *cls_weight_packed, const void *cls_bias,
+                              const void *reg_weight, const void *reg_bias, const void *dir_weight,
+                              const void *dir_bias, const void *anchors, int batch, int channels, int feat_h,
+                              int feat_w, int num_anchors, int num_classes, int code_size, int nms_pre, int max_num,
+                              float score_thr, float nms_thr, float dir_offset, float dir_limit_offset, void *boxes,
+                              void *scores, void *labels, void *counts, void *workspace, size_t workspace_bytes,
+                              void *stream);
+int pd3_anchor3d_get_bboxes(const void *cls_score, const void *bbox_pred, const void *dir_cls_pred,
+                            const void *anchors, int batch, int feat_h, int feat_w, int num_anchors, int num_classes,
+                            int code_size, int nms_pre, int max_num, float score_thr, float nms_thr, float dir_offset,
+                            float dir_limit_offset, void *boxes, void *scores, void *labels, void *counts,
+                            void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * SqueezeSegV3 (csrc/squeezeseg.hip; models/backbones/sac.py:186-197, transforms/reader.py:287-366,
  * transforms/normalize.py NormalizeRangeImage), fp32, inference only, on `stream`, no host synchronisation, every
  * output element written on every call.  The arithmetic order of every output is in the header of

@@ -324,6 +324,17 @@ _SIGNATURES_SQSEG = {
 
 SYMBOLS_SQSEG = tuple(_SIGNATURES_SQSEG)
 
+# BEVFusion's Anchor3DHead (csrc/anchor3d_head.hip).  The ninth table of this kind, for the same reason: its guarded
+# scenarios and the completeness assertion over SYMBOLS_ANCHOR3D are in tests/test_memory_safety_anchor3d_gpu.py.
+_A3D_CFG = [C.c_int] * 2 + [C.c_float] * 4 + [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p]  # nms_pre .. stream
+_SIGNATURES_ANCHOR3D = {
+    "pd3_anchor3d_head_workspace": (C.c_size_t, [C.c_int] * 7),
+    "pd3_anchor3d_head_forward": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 7 + _A3D_CFG),
+    "pd3_anchor3d_get_bboxes": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 6 + _A3D_CFG),
+}
+
+SYMBOLS_ANCHOR3D = tuple(_SIGNATURES_ANCHOR3D)
+
 
 class Paddle3DAmdError(RuntimeError):
     pass
@@ -340,7 +351,7 @@ def lib() -> C.CDLL:
                               list(_SIGNATURES_HEAD.items()) + list(_SIGNATURES_PVRCNN.items()) +
                               list(_SIGNATURES_CADDN.items()) + list(_SIGNATURES_BEVFORMER.items()) +
                               list(_SIGNATURES_BEVFORMER_DEC.items()) + list(_SIGNATURES_PETR.items()) +
-                              list(_SIGNATURES_SQSEG.items())):
+                              list(_SIGNATURES_SQSEG.items()) + list(_SIGNATURES_ANCHOR3D.items())):
         try:
             fn = getattr(handle, name)
         except AttributeError as e:  # pragma: no cover
