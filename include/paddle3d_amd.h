@@ -175,6 +175,19 @@ int pd3_pillar_conv_rulebook(const int32_t *inverse_map, int batch, int ny, int 
 int pd3_rows_to_dense_fill(const float *rows, const int32_t *cell_row, const float *fill, int batch, int channels, int h,
                            int w, float *out, void *stream);
 
+/* The three steps above as ONE launch from the inverse map to NCHW, for the shapes its tile takes (the span form,
+ * csrc/pillar_conv_span.hip): a workgroup owns 256 consecutive cells of an output row x 64 channels, builds the cells'
+ * taps in LDS, accumulates tap by tap in an LDS tile and writes the tile as 1 KB channel segments.  No rulebook, no rows,
+ * no workspace.  The same bytes as pd3_pillar_conv_rulebook -> pd3_sparse_conv3d_features_bf16x3 (bias, relu) ->
+ * pd3_rows_to_dense_fill.
+ *   feats [n_in, cin] fp32 pillar features (an inverse-map entry outside [0, n_in) counts as empty); inverse_map
+ *   [batch, ny * nx]; weight_packed = pd3_sparse_pack_weight_bf16x3 of [9, cin, cout] (tap ky * 3 + kx); bias [cout] or
+ *   NULL; fill [cout] = the value of a cell without a pillar under its nine taps (relu(bias)); out [batch, cout, ho, wo],
+ *   ho = (ny - 1) / 2 + 1.  PD3_EUNSUPPORTED unless stride == 2, cin == 64, cout is 64 or 128 and wo % 256 == 0. */
+int pd3_pillar_conv_span_x3(const float *feats, int n_in, const int32_t *inverse_map, int batch, int ny, int nx, int stride,
+                            int cin, int cout, const void *weight_packed, const float *bias, const float *fill, int relu,
+                            float *out, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * pillar feature net (PFN) -- replaces PillarFeatureNet.forward / PFNLayer.forward in eval mode,
  * paddle3d/models/voxel_encoders/pillar_encoder.py:156-210 / :81-105 (decorate with cluster and

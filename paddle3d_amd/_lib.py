@@ -335,6 +335,15 @@ _SIGNATURES_ANCHOR3D = {
 
 SYMBOLS_ANCHOR3D = tuple(_SIGNATURES_ANCHOR3D)
 
+# The sparse first backbone layer as one launch (csrc/pillar_conv_span.hip).  The tenth table of this kind, for the same
+# reason: its guarded scenario and the completeness assertion over SYMBOLS_SPAN are in tests/test_pillar_conv_span_gpu.py.
+_SIGNATURES_SPAN = {
+    "pd3_pillar_conv_span_x3": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 3 +
+                                [C.c_int] + [C.c_void_p] * 2),
+}
+
+SYMBOLS_SPAN = tuple(_SIGNATURES_SPAN)
+
 
 class Paddle3DAmdError(RuntimeError):
     pass
@@ -351,7 +360,8 @@ def lib() -> C.CDLL:
                               list(_SIGNATURES_HEAD.items()) + list(_SIGNATURES_PVRCNN.items()) +
                               list(_SIGNATURES_CADDN.items()) + list(_SIGNATURES_BEVFORMER.items()) +
                               list(_SIGNATURES_BEVFORMER_DEC.items()) + list(_SIGNATURES_PETR.items()) +
-                              list(_SIGNATURES_SQSEG.items()) + list(_SIGNATURES_ANCHOR3D.items())):
+                              list(_SIGNATURES_SQSEG.items()) + list(_SIGNATURES_ANCHOR3D.items()) +
+                              list(_SIGNATURES_SPAN.items())):
         try:
             fn = getattr(handle, name)
         except AttributeError as e:  # pragma: no cover

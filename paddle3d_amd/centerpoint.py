@@ -433,6 +433,8 @@ class SecondBackbone(_InferenceCache, nn.Module):
         # implicit-GEMM kernel of round 3 (bit-identical to scatter + convolution; the sparse form differs from it by the
         # summation order, ~1e-6 relative)
         self.sparse_first = True
+        self.sparse_first = True
+        self.span_first = True  # the sparse first layer's one-launch form where its tile fits (False: three steps)
         self.amp = False  # True: the stride-1 layers run on the fp16 matrix cores (the reference's amp_cfg O2 configs)
         self.amp_out_f16 = False  # under AMP the stage outputs leave as fp16 NHWC (set by CenterPoint.set_amp when the
         #                           neck reads that form: no fp32 NCHW copy of a stage is written at all)
@@ -465,6 +467,12 @@ class SecondBackbone(_InferenceCache, nn.Module):
                     c0.packed[key] = _conv.pack_conv3x3_f16_weight(c0.w, tile=64 if c0.cout % 128 else 128)
                 first_h = _conv.scatter_conv3x3_s2_f16_bias_relu(x, c0.packed[key], c0.b, c0.cout)
                 first = (None, x.nx // 2)
+            elif (self.sparse_first and self.span_first and x.shape[1] == c0.cin
+                  and _conv.scatter_conv_span_supported(c0.cin, c0.cout, x.ny, x.nx, c0.stride)):
+                # the same sparse convolution as one launch from the inverse map to NCHW (csrc/pillar_conv_span.hip): the
+                # same bytes as the three-step form below, which serves every other shape
+                y, c0.packed["x3span"] = _conv.scatter_conv3x3_span(x, c0.w, c0.b, c0.packed.get("x3span"))
+                first = (y, x.nx // 2)
             elif (self.sparse_first and x.shape[1] == c0.cin
                   and _conv.scatter_conv_sparse_supported(c0.cin, c0.cout, x.ny, x.nx, c0.stride)):
                 # (round 6) the first layer as a SPARSE convolution over the occupied pillars: a nuScenes canvas is 11 %

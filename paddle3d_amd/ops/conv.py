@@ -21,7 +21,8 @@ __all__ = ["pack_conv3x3_weight", "conv3x3_bias_relu", "supported", "pitch4", "p
            "f16_supported", "f16_tile", "pack_conv3x3_f16_weight", "conv3x3_f16_bias_relu", "to_f16_nhwc",
            "pack_grouped_weight_f16", "grouped_conv3x3_small_f16", "conv3x3_f16_bias_relu_dual",
            "s2_f16_supported", "conv3x3_s2_f16_bias_relu", "scatter_conv_s2_f16_supported",
-           "scatter_conv3x3_s2_f16_bias_relu", "scatter_conv_sparse_supported", "scatter_conv3x3_sparse"]
+           "scatter_conv3x3_s2_f16_bias_relu", "scatter_conv_sparse_supported", "scatter_conv3x3_sparse",
+           "scatter_conv_span_supported", "scatter_conv3x3_span"]
 
 
 def pitch4(w: int) -> int:
@@ -117,6 +118,32 @@ def scatter_conv3x3_sparse(canvas, weight: torch.Tensor, bias: torch.Tensor, pac
     out = torch.empty((n, cout, ho, wo), dtype=torch.float32, device=dev)
     check(L.pd3_rows_to_dense_fill(ptr(rows), ptr(cell_row), ptr(fill.contiguous()), n, cout, ho, wo, ptr(out),
                                    stream_ptr(dev)), "rows_to_dense_fill")
+    return out, packed
+
+
+def scatter_conv_span_supported(cin: int, cout: int, ny: int, nx: int, stride: int) -> bool:
+    """Shapes scatter_conv3x3_span serves (pd3_pillar_conv_span_x3): its tile is 256 consecutive cells of an output row x
+    64 channels over 64 input channels."""
+    return stride == 2 and cin == 64 and cout in (64, 128) and ((nx - 1) // 2 + 1) % 256 == 0 and ny > 0
+
+
+def scatter_conv3x3_span(canvas, weight: torch.Tensor, bias: torch.Tensor, packed=None, relu: bool = True):
+    """scatter_conv3x3_sparse as ONE launch from the inverse map to NCHW (csrc/pillar_conv_span.hip): no rulebook, no
+    result rows, no workspace -- the same bytes.  Returns (out, packed); packed = (the bf16x3 weight pieces, the value of
+    a cell without a pillar under its taps) belongs to (weight, bias, relu) and is computed once, not per forward."""
+    from . import sparse_conv3d as sp
+
+    f, inv = canvas.features, canvas.inv
+    n, cin, ny, nx = canvas.shape
+    cout = int(weight.shape[0])
+    if packed is None:  # [kd = 1, kh, kw, cin, cout]: offset ky * 3 + kx
+        packed = (sp.pack_weight_bf16x3(weight.permute(2, 3, 1, 0).reshape(1, 3, 3, cin, cout).contiguous()),
+                  (torch.relu(bias) if relu else bias.clone()).contiguous())
+    wpk, fill = packed
+    out = torch.empty((n, cout, (ny - 1) // 2 + 1, (nx - 1) // 2 + 1), dtype=torch.float32, device=f.device)
+    check(lib().pd3_pillar_conv_span_x3(ptr(f), int(f.shape[0]), ptr(inv), n, ny, nx, 2, cin, cout, ptr(wpk), ptr(bias),
+                                        ptr(fill), int(bool(relu)), ptr(out), stream_ptr(f.device)),
+          "pillar_conv_span_x3")
     return out, packed
 
 
