@@ -39,8 +39,9 @@ __device__ __forceinline__ uint32_t sp_hash(uint32_t k) {
   return k;
 }
 
+// (unsigned arithmetic: keys from 2^31 up to the 0xFFFFFFFE cells the entry points accept are no signed overflow)
 __device__ __forceinline__ uint32_t sp_key(int b, int z, int y, int x, const SpShape& s) {
-  return (uint32_t)(((b * s.d + z) * s.h + y) * s.w + x);
+  return (((uint32_t)b * (uint32_t)s.d + (uint32_t)z) * (uint32_t)s.h + (uint32_t)y) * (uint32_t)s.w + (uint32_t)x;
 }
 
 // coords [n,4] (b,z,y,x) -> keys; rows with b < 0 (padding) get kSpEmpty

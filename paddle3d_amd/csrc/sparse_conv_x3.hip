@@ -223,7 +223,50 @@ __global__ __launch_bounds__(64 * (8 / RB), RB == 1 ? 1 : 2) void sp_gemm_rows_x
   int k = wg_mask ? __builtin_ctz(wg_mask) : -1, c = 0, buf = 0;
   int k2 = k, c2 = c;
   int j_a[RB], j_b[RB];
-  if (k < 0) return;  // (a tile whose rows have no neighbour at all cannot exist: the centre offset is its own row)
+  // epilogue: D[m = (reg & 3) + 8 (reg >> 2) + 4 kh][n = l31] of block (i, rb): channel 32 i + m, output row n of the
+  // wave's block rb; four consecutive channels (regs 4 q .. 4 q + 3) leave as one 16-byte store
+  auto epilogue = [&]() {
+#pragma unroll
+    for (int rb = 0; rb < RB; ++rb) {
+      const int row = rows[wave * (32 * RB) + rb * 32 + l31];
+      if (row < 0) continue;
+#pragma unroll
+      for (int i = 0; i < NC; ++i) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int co = i * 32 + 8 * q + 4 * kh;
+          float v[4];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = acc[i][rb][4 * q + e];
+          if (a.bias) {
+            const sx_f32x4 b4 = *reinterpret_cast<const sx_f32x4*>(a.bias + co);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] += b4[e];
+          }
+          if (a.scale) {
+            const sx_f32x4 s4 = *reinterpret_cast<const sx_f32x4*>(a.scale + co);
+            const sx_f32x4 h4 = *reinterpret_cast<const sx_f32x4*>(a.shift + co);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = fmaf(v[e], s4[e], h4[e]);
+          }
+          if (a.residual) {
+            const sx_f32x4 r4 = *reinterpret_cast<const sx_f32x4*>(a.residual + (int64_t)row * COUT + co);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] += r4[e];
+          }
+          if (a.relu) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+          }
+          *reinterpret_cast<sx_f32x4*>(a.out + (int64_t)row * COUT + co) = sx_f32x4{v[0], v[1], v[2], v[3]};
+        }
+      }
+    }
+  };
+  if (k < 0) {  // no row of the tile has a neighbour (never a convolution's rulebook -- the centre offset is the row itself --
+    epilogue();  // but a caller's own table may hold such rows, and the tile order puts them into one tile): the epilogue of 0
+    return;
+  }
   next_step(k2, c2);
   fetch_w(k, c);
   fetch_b(k, c, raw_a, j_a);
@@ -294,44 +337,7 @@ __global__ __launch_bounds__(64 * (8 / RB), RB == 1 ? 1 : 2) void sp_gemm_rows_x
       step(raw_a, j_a, raw_b, j_b, bpa, bpa);
     }
   }
-  // epilogue: D[m = (reg & 3) + 8 (reg >> 2) + 4 kh][n = l31] of block (i, rb): channel 32 i + m, output row n of the
-  // wave's block rb; four consecutive channels (regs 4 q .. 4 q + 3) leave as one 16-byte store
-#pragma unroll
-  for (int rb = 0; rb < RB; ++rb) {
-    const int row = rows[wave * (32 * RB) + rb * 32 + l31];
-    if (row < 0) continue;
-#pragma unroll
-    for (int i = 0; i < NC; ++i) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int co = i * 32 + 8 * q + 4 * kh;
-        float v[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = acc[i][rb][4 * q + e];
-        if (a.bias) {
-          const sx_f32x4 b4 = *reinterpret_cast<const sx_f32x4*>(a.bias + co);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] += b4[e];
-        }
-        if (a.scale) {
-          const sx_f32x4 s4 = *reinterpret_cast<const sx_f32x4*>(a.scale + co);
-          const sx_f32x4 h4 = *reinterpret_cast<const sx_f32x4*>(a.shift + co);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = fmaf(v[e], s4[e], h4[e]);
-        }
-        if (a.residual) {
-          const sx_f32x4 r4 = *reinterpret_cast<const sx_f32x4*>(a.residual + (int64_t)row * COUT + co);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] += r4[e];
-        }
-        if (a.relu) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-        }
-        *reinterpret_cast<sx_f32x4*>(a.out + (int64_t)row * COUT + co) = sx_f32x4{v[0], v[1], v[2], v[3]};
-      }
-    }
-  }
+  epilogue();
 }
 
 // weight [K, cin, cout] fp32 (Paddle layout, kd kh kw flattened) -> bf16 pieces [K][cin / KC][3][cout][KC / 16][2][8]:
