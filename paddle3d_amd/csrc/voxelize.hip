@@ -276,11 +276,13 @@ static VtWorkspace vt_carve(void* base, int batch, int64_t n, int dim, int max_p
   return w;
 }
 
+// aligned16: the voxels tensor lies at a multiple of 16 bytes, so the float4 row writer runs where P * D % 4 == 0; else the
+// scalar writer runs with four times as many units, and it is THAT count vt_div's x < 2^24 must hold for
 static bool tiled_applicable(const VoxGrid& g, int64_t n, int dim, int max_pts, int max_voxels,
-                             VtPlan& plan) {
+                             VtPlan& plan, bool aligned16 = true) {
   plan = vt_plan(g.ncells, n, max_pts);
   const int64_t row = (int64_t)max_pts * dim;
-  const int64_t rowq = (row % 4 == 0) ? row / 4 : row;
+  const int64_t rowq = (row % 4 == 0 && aligned16) ? row / 4 : row;
   return plan.ok && (int64_t)max_voxels * rowq < ((int64_t)1 << 24) - 4096;
 }
 
@@ -383,10 +385,12 @@ static bool wave3d_applicable(const VoxGrid& g, int64_t n, int dim, int max_pts,
 constexpr int kVwShapes = 5;
 
 static bool wave_applicable(const VoxGrid& g, int64_t n, int dim, int max_pts, int max_voxels, int batch, int shape,
-                            VwPlan& plan) {
+                            VwPlan& plan, bool aligned16 = true) {
   plan = vw_plan(g.ncells, n, max_pts, batch, shape);
   const int64_t row = (int64_t)max_pts * dim;
-  const int64_t rowq = (row % 4 == 0) ? row / 4 : row;
+  // (D = 4 / 5 rows leave through the slot-per-lane writer whatever the alignment: voxel * slot is what counts there)
+  const bool vec4 = aligned16 || dim == 4 || dim == 5;
+  const int64_t rowq = (row % 4 == 0 && vec4) ? row / 4 : row;
   return plan.ok && (int64_t)max_voxels * rowq < ((int64_t)1 << 24) - 4096;
 }
 
@@ -668,13 +672,14 @@ extern "C" int pd3_hard_voxelize_path(const float* points, const int32_t* num_po
   if (!make_grid(voxel_size, point_cloud_range, g) || path < 0 || path > 17) return PD3_EINVAL;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int64_t n = max_points;
+  const bool al16 = reinterpret_cast<uintptr_t>(voxels) % 16 == 0;  // which row writer runs (see tiled_applicable)
   if (workspace_bytes < pd3_hard_voxelize_workspace(batch, max_points, num_point_dim, voxel_size,
                                                     point_cloud_range, max_num_points_in_voxel,
                                                     max_voxels))
     return PD3_EWORKSPACE;
   if (path == 17) {  // measurement: the wave form (4096-point route tiles) with the payload carried through the route
     VwPlan wp;
-    if (!wave_applicable(g, n, num_point_dim, max_num_points_in_voxel, max_voxels, batch, 0, wp)) return PD3_EUNSUPPORTED;
+    if (!wave_applicable(g, n, num_point_dim, max_num_points_in_voxel, max_voxels, batch, 0, wp, al16)) return PD3_EUNSUPPORTED;
     return run_wave(points, num_points, batch, n, num_point_dim, g, max_num_points_in_voxel, max_voxels, wp, voxels,
                     coords, num_points_per_voxel, num_voxels, coors_batched, workspace, s, 1 | 4);
   }
@@ -687,7 +692,7 @@ extern "C" int pd3_hard_voxelize_path(const float* points, const int32_t* num_po
   }
   if (path >= 11) {  // measurement variants of the wave form
     VwPlan wp;
-    if (!wave_applicable(g, n, num_point_dim, max_num_points_in_voxel, max_voxels, batch, -1, wp))
+    if (!wave_applicable(g, n, num_point_dim, max_num_points_in_voxel, max_voxels, batch, -1, wp, al16))
       return PD3_EUNSUPPORTED;
     const int variant = path == 11 ? 1 : (path == 12 ? 2 : 3);
     if (variant & 2)
@@ -698,7 +703,7 @@ extern "C" int pd3_hard_voxelize_path(const float* points, const int32_t* num_po
   }
   if (path >= 5) {  // wave form: 5 = shape chosen from the sizes, 6 .. = route-kernel shape forced (measurement)
     VwPlan wp;
-    if (!wave_applicable(g, n, num_point_dim, max_num_points_in_voxel, max_voxels, batch, path - 6, wp))
+    if (!wave_applicable(g, n, num_point_dim, max_num_points_in_voxel, max_voxels, batch, path - 6, wp, al16))
       return PD3_EUNSUPPORTED;
     return run_wave(points, num_points, batch, n, num_point_dim, g, max_num_points_in_voxel, max_voxels, wp, voxels,
                     coords, num_points_per_voxel, num_voxels, coors_batched, workspace, s);
@@ -707,7 +712,7 @@ extern "C" int pd3_hard_voxelize_path(const float* points, const int32_t* num_po
     VwPlan wp;
     // (heavy group waves at raised issue priority: 112.8-116.2 against 113.1-122.1 us per 16 frames in four A/B pairs
     //  on two boxes, profiles/r04_vox_paths.txt; path 5 is the same without it)
-    if (wave_applicable(g, n, num_point_dim, max_num_points_in_voxel, max_voxels, batch, -1, wp))
+    if (wave_applicable(g, n, num_point_dim, max_num_points_in_voxel, max_voxels, batch, -1, wp, al16))
       return run_wave(points, num_points, batch, n, num_point_dim, g, max_num_points_in_voxel, max_voxels, wp, voxels,
                       coords, num_points_per_voxel, num_voxels, coors_batched, workspace, s, 1);
     if (wave3d_applicable(g, n, num_point_dim, max_num_points_in_voxel, max_voxels, batch, -1, wp))
@@ -716,7 +721,7 @@ extern "C" int pd3_hard_voxelize_path(const float* points, const int32_t* num_po
   }
   {
     VtPlan vp;
-    const bool can = tiled_applicable(g, n, num_point_dim, max_num_points_in_voxel, max_voxels, vp);
+    const bool can = tiled_applicable(g, n, num_point_dim, max_num_points_in_voxel, max_voxels, vp, al16);
     if (path >= 2 && !can) return PD3_EUNSUPPORTED;
     if (can && path != 1)
       return run_tiled(points, num_points, batch, n, num_point_dim, g, max_num_points_in_voxel,
