@@ -1144,6 +1144,55 @@ int pd3_ssd_postprocess(const float *head_map, int64_t batch_stride, int cls_cha
                         size_t workspace_bytes, void *stream, int selection);
 
 /* ---------------------------------------------------------------------------------------------
+ * IA-SSD at inference (csrc/iassd.hip).  fp32 data, contiguous tensors unless a stride is named, 64-bit offsets inside
+ * the kernels, no float atomics; nothing here synchronises with the host.
+ *
+ * sa_msg_pool -- one scale of SAModuleMSG_WithSampling.forward (models/detection/iassd/iassd_modules.py:204-221) from
+ * the ball query to the max pool, with no idx and no [batch, *, m, nsample] tensor in global memory.  The scale's mlp
+ * is three times Conv2d / BN / ReLU, (3 + C) -> c1 -> c2 -> c3; the first convolution is linear in [d; f], so the
+ * caller passes features_in = features @ W1[:, 3:]^T ([batch, n, c1], NULL reads as zeros) and w_pos = W1[:, :3].
+ * new_xyz [batch, m, 3], xyz [batch, n, 3], w_pos [c1, 3], scale1 / shift1 [c1], w2 [c2, c1], scale2 / shift2 [c2],
+ * w3 [c3, c2], scale3 / shift3 [c3] (each BatchNorm in eval form, scale = gamma / sqrt(var + eps), shift = beta -
+ * mean * scale, formed by the caller in fp32) -> the row of query (b, q) at out + (b * m + q) * ld_out, c3 floats
+ * (ld_out >= c3: the columns beside it are not touched, so the scales of a layer write side by side into one buffer):
+ *   h1[s, j] = relu(scale1[j] * (features_in[b, idx_s, j] + ((w_pos[j,0] * dx + w_pos[j,1] * dy) + w_pos[j,2] * dz))
+ *                   + shift1[j])                                                             (no FMA)
+ *   h2[s, c] = relu(scale2[c] * (sum_j w2[c, j] * h1[s, j]) + shift2[c])                     (no FMA outside the sum)
+ *   h3[s, c] = relu(scale3[c] * (sum_j w3[c, j] * h2[s, j]) + shift3[c])
+ *   out[c]   = max_s h3[s, c]
+ * with idx exactly pd3_ball_query_batch's row for the same arguments (the first nsample points in index order with
+ * ((nx - x)^2 + (ny - y)^2) + (nz - z)^2 < radius * radius, a NaN is no hit), d = xyz[b, idx_s] - new_xyz.  The max
+ * runs over the hits only (unused slots repeat the first hit); a row without a hit takes its one slot, point 0 of the
+ * frame, a real point with its own features_in row and d.  Each sum over j is an ascending-j fp32 fmaf chain from 0
+ * (what v_mfma_f32_16x16x4_f32 computes), so the result depends neither on the tiling nor on where a row sits in the
+ * launch.  relu(v) = v > 0 ? v : +0 (a NaN stays) and the max keeps a NaN, as in pd3_stack_sa_pool.
+ * c1, c2, c3 each a multiple of 16 in 16 .. 256 and nsample <= 64, else PD3_EUNSUPPORTED.  PD3_EINVAL on negative
+ * dims, nsample < 1, ld_out < c3, or n == 0 with rows to compute; batch * m == 0 launches nothing.
+ */
+int pd3_sa_msg_pool(const float *new_xyz, const float *xyz, const float *features_in, const float *w_pos,
+                    const float *scale1, const float *shift1, const float *w2, const float *scale2,
+                    const float *shift2, const float *w3, const float *scale3, const float *shift3, int batch, int m,
+                    int n, int c1, int c2, int c3, float radius, int nsample, float *out, int64_t ld_out,
+                    void *stream);
+
+/* iassd_decode -- IASSD_Head.generate_predicted_boxes with PointResidual_BinOri_Coder.decode_paddle
+ * (iassd_head.py:606-621, iassd_coder.py:76-121) in one launch.  cls_preds [m, num_classes], box_preds
+ * [m, 6 + 2 * bins], the centre of row i at centers + i * ld_centers (3 floats, ld_centers >= 3: columns 1:4 of a
+ * [m, 4] tensor are read in place), mean_size [num_classes, 3] or NULL (use_mean_size=False) -> boxes [m, 7]:
+ *   k = argmax of the raw logits of the row (the first maximum wins, a NaN counts as the maximum);
+ *   with mean_size: (dxa, dya, dza) = mean_size[k], diagonal = sqrt(dxa * dxa + dya * dya),
+ *     x = xt * diagonal + xa, y = yt * diagonal + ya, z = zt * dza + za, dx = exp(dxt) * dxa, dy, dz likewise;
+ *   without: x = xt + xa, y, z likewise, dx = exp(dxt), dy, dz likewise;
+ *   bin = argmax of box_preds[6 : 6 + bins] under the same rule, res = box_preds[6 + bins + bin];
+ *   heading = ((float(bin) * bin_inter - pi) + half) + res * half, bin_inter = float(2 pi / bins), half =
+ *   float(pi / bins), pi = float(pi).
+ * exp is glibc's expf (csrc/libm_exact.hpp); no FMA.  PD3_EINVAL on m < 0, num_classes < 1, bins < 1 or
+ * ld_centers < 3; m == 0 launches nothing.
+ */
+int pd3_iassd_decode(const float *cls_preds, const float *box_preds, const float *centers, int64_t ld_centers,
+                     const float *mean_size, int64_t m, int num_classes, int bins, float *boxes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * BEVFusion's Anchor3DHead at inference (csrc/anchor3d_head.hip; models/heads/dense_heads/anchor3d_head.py:146-161,
  * :378-520, models/detection/bevfusion/utils.py:92-103, :189-276, utils/box_coder.py:270-310), fp32, on `stream`, no
  * host synchronisation, every count on the device, every output element written on every call.  The arithmetic order

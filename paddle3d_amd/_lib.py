@@ -344,6 +344,17 @@ _SIGNATURES_SPAN = {
 
 SYMBOLS_SPAN = tuple(_SIGNATURES_SPAN)
 
+# IA-SSD's fused set abstraction and box decode (csrc/iassd.hip).  The eleventh table of this kind, for the same reason:
+# its guarded scenarios and the completeness assertion over SYMBOLS_IASSD are in tests/test_memory_safety_iassd_gpu.py.
+_SIGNATURES_IASSD = {
+    "pd3_sa_msg_pool": (C.c_int, [C.c_void_p] * 12 + [C.c_int] * 6 + [C.c_float, C.c_int, C.c_void_p, C.c_int64,
+                                                                     C.c_void_p]),
+    "pd3_iassd_decode": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int] +
+                         [C.c_void_p] * 2),
+}
+
+SYMBOLS_IASSD = tuple(_SIGNATURES_IASSD)
+
 
 class Paddle3DAmdError(RuntimeError):
     pass
@@ -361,7 +372,7 @@ def lib() -> C.CDLL:
                               list(_SIGNATURES_CADDN.items()) + list(_SIGNATURES_BEVFORMER.items()) +
                               list(_SIGNATURES_BEVFORMER_DEC.items()) + list(_SIGNATURES_PETR.items()) +
                               list(_SIGNATURES_SQSEG.items()) + list(_SIGNATURES_ANCHOR3D.items()) +
-                              list(_SIGNATURES_SPAN.items())):
+                              list(_SIGNATURES_SPAN.items()) + list(_SIGNATURES_IASSD.items())):
         try:
             fn = getattr(handle, name)
         except AttributeError as e:  # pragma: no cover
