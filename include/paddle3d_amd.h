@@ -733,6 +733,8 @@ int pd3_frustum_to_lidar(const float *frustum, int64_t points_per_camera, int ba
  *   ranks_bev / ranks_depth / ranks_feat [num_points] int32 (first counts[0] valid, sorted by rank, points of
  *   a cell in index order = a stable argsort), interval_starts / interval_lengths [num_points] int32 (first
  *   counts[1] valid), counts [2] int32 (device): kept points, intervals.
+ * PD3_EUNSUPPORTED when batch * X * Y * Z exceeds 2^31: every cell id must fit the int32 ranks_bev (a larger grid
+ * would come back with negative ranks).  A grid of exactly 2^31 cells is served.
  */
 size_t pd3_voxel_pooling_prepare_workspace(int64_t num_points);
 int pd3_voxel_pooling_prepare(const float *coor, int64_t num_points, int batch, int depth_bins, int feat_hw,

@@ -352,8 +352,14 @@ extern "C" int pd3_voxel_pooling_prepare(const float* coor, int64_t num_points, 
   g.gy = (int)grid_size[1];
   g.gz = (int)grid_size[2];
   if (g.gx <= 0 || g.gy <= 0 || g.gz <= 0) return PD3_EINVAL;
-  const int64_t cells = (int64_t)batch * g.gx * g.gy * g.gz;
-  if (cells >= (int64_t)0xFFFFFFFFll) return PD3_EUNSUPPORTED;
+  // ranks_bev is int32: the largest cell id, cells - 1, must fit it (`cells` itself, the key of a point outside the grid,
+  // only has to fit the sort's uint32 keys).  The product is bounded factor by factor so that it cannot wrap.
+  constexpr int64_t kMaxCells = (int64_t)1 << 31;
+  int64_t cells = batch;
+  for (const int dim : {g.gx, g.gy, g.gz}) {
+    if (cells > kMaxCells / dim) return PD3_EUNSUPPORTED;
+    cells *= dim;
+  }
   const RadixPlan full = radix_plan((uint32_t)cells, num_points);  // keys 0 .. cells, `cells` = outside the grid
   VppWorkspace w = vpp_carve(workspace, num_points, full);
   if (workspace_bytes < w.bytes) return PD3_EWORKSPACE;

@@ -4,7 +4,7 @@
 // the slot a point gets equal to the number of earlier points of its cell (the reference's sequential scan,
 // voxelize_op.cc:47-78) without a sort.  The ISA documents neither; tools/hwcheck/lds_atomic_order.hip measured it
 // (0 mismatches in 4.2 M on gfx950).  This entry point runs the same probe through the library, compiled with the
-// library's flags, so that tests/test_voxelize_gpu.py::test_lds_atomic_lane_order can assert it on every GPU test run
+// library's flags, so that tests/test_properties_gpu.py::test_lds_atomic_lane_order can assert it on every GPU test run
 // and a caller can assert it at start-up on a new part or driver.
 #include "../../include/paddle3d_amd.h"
 #include "common.hpp"
