@@ -535,12 +535,9 @@ int a3d_finish(const A3dShape& sh, const A3dWorkspace& w, const float* feat, con
   a3d_class_sets_kernel<<<dim3(sh.nc, sh.B), kTopkThreads, 0, s>>>(w.cd, sh.K, sh.nc, score_thr, w.set_counts, w.order,
                                                                    w.pre, w.pool.xyr);
   nms_enqueue_mask_pooled(w.pre, w.set_counts, sets, sh.K, cb, nms_thr, w.mask, w.pool, s);
-  const size_t lds = nms_sweep_lds(sh.K);
-  if (lds > 48 * 1024) {
-    const hipError_t e = pd3_max_dynamic_lds(reinterpret_cast<const void*>(nms_sweep_kernel), (int)lds);
-    if (e != hipSuccess) return (int)e;
-  }
-  nms_sweep_kernel<<<sets, kNmsSweepThreads, lds, s>>>(w.mask, w.set_counts, 0, sh.K, cb, w.keep, w.nkeep);
+  if (const int rc = launch_lds(nms_sweep_kernel, sets, kNmsSweepThreads, nms_sweep_lds(sh.K), s, w.mask, w.set_counts, 0,
+                                sh.K, cb, w.keep, w.nkeep))
+    return rc;
   a3d_concat_kernel<<<dim3(sh.nc, sh.B), 256, 0, s>>>(w.cd, sh.K, sh.nc, w.order, w.keep, w.nkeep, w.cat_key, w.cat_src);
   a3d_output_kernel<<<sh.B, kTopkThreads, 0, s>>>(w.cd, sh.K, sh.nc, sh.cs, sh.max_num, dir_offset, dir_limit_offset,
                                                   w.nkeep, w.cat_key, w.cat_src, boxes, scores, labels, counts);

@@ -373,13 +373,8 @@ static CnWork cn_carve(void* base, int n) {
 
 static hipError_t bd_sweep(const unsigned long long* mask, const int* counts, int n_fixed, int sets, int cap, int cb,
                            int32_t* keep, int32_t* nkeep, hipStream_t s) {
-  const size_t lds = nms_sweep_lds(cap);
-  if (lds > 48 * 1024) {
-    const hipError_t e = pd3_max_dynamic_lds(reinterpret_cast<const void*>(nms_sweep_kernel), (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  nms_sweep_kernel<<<sets, kNmsSweepThreads, lds, s>>>(mask, counts, n_fixed, cap, cb, keep, nkeep);
-  return hipSuccess;
+  return (hipError_t)launch_lds(nms_sweep_kernel, sets, kNmsSweepThreads, nms_sweep_lds(cap), s, mask, counts, n_fixed, cap,
+                                cb, keep, nkeep);
 }
 
 }  // namespace pd3

@@ -398,11 +398,10 @@ int pd3_mha_forward(const void* q, const void* k, const void* v, int batch, int 
   if (blocks > 0x7fffffff) return PD3_EUNSUPPORTED;
   const int SN = (num_key + 15) / 16 * 16 + 4;
   const int lds = 16 * (SN + head_dim + kQPad) * (int)sizeof(float);
-  if (hipError_t e = pd3_max_dynamic_lds(reinterpret_cast<const void*>(mha_kernel), lds)) return (int)e;
-  hipLaunchKernelGGL(mha_kernel, dim3((unsigned)blocks), dim3(kMhaThreads), (size_t)lds, (hipStream_t)stream,
-                     static_cast<const float*>(q), static_cast<const float*>(k), static_cast<const float*>(v),
-                     static_cast<float*>(out), num_query, num_key, num_heads, head_dim, QB, SN, scale);
-  return pd3::launch_status();
+  const int rc = pd3::launch_lds(mha_kernel, (unsigned)blocks, kMhaThreads, (size_t)lds, (hipStream_t)stream,
+                                 static_cast<const float*>(q), static_cast<const float*>(k), static_cast<const float*>(v),
+                                 static_cast<float*>(out), num_query, num_key, num_heads, head_dim, QB, SN, scale);
+  return rc ? rc : pd3::launch_status();
 }
 
 int pd3_bevformer_dec_ca(const void* value, const int64_t* spatial_shapes, const int64_t* level_start_index,

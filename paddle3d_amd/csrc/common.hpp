@@ -51,6 +51,20 @@ static inline hipError_t pd3_max_dynamic_lds(const void* fn, int bytes) {
   return e;
 }
 
+// Launches `kernel` with `lds_bytes` of dynamic LDS.  Above the 48 KiB a kernel may use without asking, the cap of this
+// instantiation is raised first (pd3_max_dynamic_lds: once per size, not per launch).  Returns 0, or the attribute
+// call's positive hipError_t without launching; the sticky launch error stays for the caller's launch_status().
+template <typename... P, typename... A>
+static inline int launch_lds(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds_bytes, hipStream_t stream,
+                             const A&... args) {
+  if (lds_bytes > 48 * 1024) {
+    const hipError_t e = pd3_max_dynamic_lds(reinterpret_cast<const void*>(kernel), (int)lds_bytes);
+    if (e != hipSuccess) return (int)e;
+  }
+  kernel<<<grid, block, lds_bytes, stream>>>(args...);
+  return 0;
+}
+
 __host__ __device__ static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 __host__ __device__ static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 

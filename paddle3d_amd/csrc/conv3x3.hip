@@ -251,14 +251,12 @@ static int launch_conv3x3(int64_t tiles, hipStream_t s, const float* x, const fl
                           float* out, int cin, int cout, int h, int w, int wi, int wv, int relu,
                           const int* imap = nullptr) {
   constexpr size_t lds = (size_t)(XB * kCvCi * ((R - 1) * S + 3) * (S * WT + 8) + 2 * kCvK * kCvCo) * sizeof(float);
-  // raise the dynamic-LDS cap (per device and per instantiation: set on every launch, it is a host-side table write)
-  hipError_t e = pd3_max_dynamic_lds(reinterpret_cast<const void*>(conv3x3_mfma_kernel<R, WT, S, XB, FUSED>), (int)lds);
-  if (e != hipSuccess) return (int)e;
   const int64_t nwg = (tiles + 7) / 8 * 8 * (cout / kCvCo);
   if (nwg >= (int64_t)1 << 31) return PD3_EUNSUPPORTED;
-  conv3x3_mfma_kernel<R, WT, S, XB, FUSED><<<(unsigned)nwg, 256, lds, s>>>(x, wp, bias, out, cin, cout, h, w, wi, wv,
-                                                                           relu, (int)tiles, imap);
-  return launch_status();
+  // (the dynamic-LDS cap is raised per device and per instantiation, once)
+  const int rc = launch_lds(conv3x3_mfma_kernel<R, WT, S, XB, FUSED>, (unsigned)nwg, 256, lds, s, x, wp, bias, out, cin,
+                            cout, h, w, wi, wv, relu, (int)tiles, imap);
+  return rc ? rc : launch_status();
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -764,17 +764,15 @@ template <int CO, bool GM>
 static int launch_grouped_pp(const _Float16* x, const _Float16* wg, const float* bias, int batch, int groups, int h, int w,
                              float* out, int out_groups, int out_group0, hipStream_t s) {
   constexpr int LDS = 3 * 10 * 40 * 128;
-  const hipError_t e = pd3_max_dynamic_lds(reinterpret_cast<const void*>(grouped_conv3x3_small_f16_pp_kernel<CO, GM>), LDS);
-  if (e != hipSuccess) return (int)e;
   const int64_t tiles = ceil_div(w, 32) * ceil_div(h, 8), total = tiles * groups * batch;
   if (total >= (int64_t)1 << 31) return PD3_EUNSUPPORTED;
   // one workgroup per CU where the work allows it, each with the same number of tiles (at least kGpTiles: the weights and
   // the first patch of a workgroup are not hidden)
   const int64_t per_wg = std::max<int64_t>(kGpTiles, ceil_div(total, 256));
   const int64_t xbytes = (int64_t)batch * h * w * groups * 64 * 2;
-  grouped_conv3x3_small_f16_pp_kernel<CO, GM><<<(unsigned)ceil_div(total, per_wg), 320, LDS, s>>>(
-      x, wg, bias, groups, h, w, out, out_groups, out_group0, (int)xbytes, (int)total, (int)per_wg);
-  return launch_status();
+  const int rc = launch_lds(grouped_conv3x3_small_f16_pp_kernel<CO, GM>, (unsigned)ceil_div(total, per_wg), 320, LDS, s, x,
+                            wg, bias, groups, h, w, out, out_groups, out_group0, (int)xbytes, (int)total, (int)per_wg);
+  return rc ? rc : launch_status();
 }
 
 // fp32 NCHW -> fp16 NHWC (the boundary in front of a chain of fp16 layers): one workgroup per (n, y, 64 columns),
@@ -808,8 +806,6 @@ template <int MB, int OUT_MODE>
 static int launch_conv_f16(const void* x, const void* wp, const float* bias, int batch, int cin, int cout, int h, int w,
                            int relu, void* out, hipStream_t s, float* out2 = nullptr) {
   using S = CfShape<MB>;
-  hipError_t e = pd3_max_dynamic_lds(reinterpret_cast<const void*>(conv3x3_f16_kernel<MB, OUT_MODE>), (int)S::LDS);
-  if (e != hipSuccess) return (int)e;
   const int64_t ptiles = (int64_t)batch * ceil_div(h, S::R) * ceil_div(w, kCfCols);
   const int nct = cout / S::M;
   const int64_t nslots = (ptiles + 7) / 8 * nct;  // work items per XCD lane (pixel tile group x channel tile)
@@ -822,10 +818,10 @@ static int launch_conv_f16(const void* x, const void* wp, const float* bias, int
     while (nct % ipw != 0) --ipw;
   }
   const int64_t nwg = 8 * ceil_div(nslots, ipw);
-  conv3x3_f16_kernel<MB, OUT_MODE><<<(unsigned)nwg, kCfThreads, S::LDS, s>>>(
-      static_cast<const _Float16*>(x), static_cast<const _Float16*>(wp), bias, out, cin, cout, h, w, relu, (int)ptiles,
-      ipw, out2);
-  return launch_status();
+  const int rc = launch_lds(conv3x3_f16_kernel<MB, OUT_MODE>, (unsigned)nwg, kCfThreads, S::LDS, s,
+                            static_cast<const _Float16*>(x), static_cast<const _Float16*>(wp), bias, out, cin, cout, h, w,
+                            relu, (int)ptiles, ipw, out2);
+  return rc ? rc : launch_status();
 }
 
 extern "C" int pd3_conv3x3_f16_bias_relu(const void* x_f16_nhwc, const void* w_packed_f16, const float* bias, int batch,
@@ -872,15 +868,13 @@ static int launch_conv_s2_f16(const void* x, const int32_t* inv, const void* wp,
                               int cout, int h, int w, int relu, void* out, hipStream_t s) {
   using S = Cs2Shape<MW>;
   const int ho = (h + 2 - 3) / 2 + 1, wo = (w + 2 - 3) / 2 + 1;
-  hipError_t e = pd3_max_dynamic_lds(reinterpret_cast<const void*>(conv3x3_s2_f16_kernel<MW, GATHER>), (int)S::LDS);
-  if (e != hipSuccess) return (int)e;
   const int64_t ptiles = (int64_t)batch * ceil_div(ho, kCs2R) * ceil_div(wo, kCfCols);
   const int64_t nwg = (ptiles + 7) / 8 * 8 * (cout / S::M);
   if (nwg >= (int64_t)1 << 31) return PD3_EUNSUPPORTED;
-  conv3x3_s2_f16_kernel<MW, GATHER><<<(unsigned)nwg, S::THREADS, S::LDS, s>>>(
-      static_cast<const _Float16*>(x), inv, static_cast<const _Float16*>(wp), bias, static_cast<_Float16*>(out), cin, cout,
-      h, w, ho, wo, relu, (int)ptiles);
-  return launch_status();
+  const int rc = launch_lds(conv3x3_s2_f16_kernel<MW, GATHER>, (unsigned)nwg, S::THREADS, S::LDS, s,
+                            static_cast<const _Float16*>(x), inv, static_cast<const _Float16*>(wp), bias,
+                            static_cast<_Float16*>(out), cin, cout, h, w, ho, wo, relu, (int)ptiles);
+  return rc ? rc : launch_status();
 }
 
 extern "C" int pd3_conv3x3_s2_f16_bias_relu(const void* x_f16_nhwc, const void* w_packed_f16, const float* bias, int batch,

@@ -223,16 +223,12 @@ template <int CB>
 static int launch_wino43(const float* x, const float* u_packed, const float* bias, int batch, int cin, int cout,
                          int h, int w, int wv, int relu, float* out, hipStream_t s) {
   constexpr size_t lds = (size_t)((CB == 4 ? 2 : 1) * (CB * kW4Ci * 16 * kW4Cs + kW4Vsz) + kW4RawSz) * sizeof(float);
-  {  // dynamic-LDS cap: per device, so it is set on every launch (a host-side table write)
-    hipError_t e = pd3_max_dynamic_lds(reinterpret_cast<const void*>(conv3x3_winograd43_kernel<CB>), (int)lds);
-    if (e != hipSuccess) return (int)e;
-  }
   int64_t ptiles;
   const int64_t nwg = w4_grid(batch, h, w, cout / (16 * CB), &ptiles);
   if (nwg >= (int64_t)1 << 31) return PD3_EUNSUPPORTED;
-  conv3x3_winograd43_kernel<CB><<<(unsigned)nwg, 128 * CB, lds, s>>>(x, u_packed, bias, out, cin, cout, h, w, wv,
-                                                                       relu, (int)ptiles);
-  return launch_status();
+  const int rc = launch_lds(conv3x3_winograd43_kernel<CB>, (unsigned)nwg, 128 * CB, lds, s, x, u_packed, bias, out, cin,
+                            cout, h, w, wv, relu, (int)ptiles);
+  return rc ? rc : launch_status();
 }
 
 // channels_per_tile selects the workgroup shape the weights were packed for: 32 (two workgroups per CU) or 64

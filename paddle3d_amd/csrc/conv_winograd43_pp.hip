@@ -259,15 +259,12 @@ template <bool DBG, int RELU, bool WHOLE>
 static int launch_wino43_pp_as(const float* x, const float* u_lane, const float* bias, int batch, int cin, int cout, int h,
                                int w, int w_valid, int relu, float* out, hipStream_t s, long long* dbg) {
   constexpr size_t lds = ((size_t)kPpUsz + 2 * (kPpRawSz + kPpVsz) + 64) * sizeof(float);  // 138,240 B + the bias
-  const void* fn = reinterpret_cast<const void*>(conv3x3_winograd43_pp_kernel<DBG, RELU, WHOLE>);
-  hipError_t e = pd3_max_dynamic_lds(fn, (int)lds);
-  if (e != hipSuccess) return (int)e;
   int64_t ptiles;
   const int64_t nwg = w4_grid(batch, h, w, cout / 64, &ptiles);
   if (nwg >= (int64_t)1 << 31) return PD3_EUNSUPPORTED;
-  conv3x3_winograd43_pp_kernel<DBG, RELU, WHOLE><<<(unsigned)nwg, 512, lds, s>>>(x, u_lane, bias, out, cin, cout, h, w,
-                                                                                 w_valid, relu, (int)ptiles, dbg);
-  return launch_status();
+  const int rc = launch_lds(conv3x3_winograd43_pp_kernel<DBG, RELU, WHOLE>, (unsigned)nwg, 512, lds, s, x, u_lane, bias, out,
+                            cin, cout, h, w, w_valid, relu, (int)ptiles, dbg);
+  return rc ? rc : launch_status();
 }
 
 // whole tiles at full width take the output step's compile-time forms, every other layer the general one; the traced

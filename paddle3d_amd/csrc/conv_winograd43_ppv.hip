@@ -251,17 +251,10 @@ extern "C" int pd3_conv3x3_winograd43_ppv_bias_relu(const float* v_pre, const fl
   const int64_t nwg = ptiles8 * (nct / ipw);
   if (nwg >= (int64_t)1 << 31) return PD3_EUNSUPPORTED;
   // whole tiles at full width take the output step's compile-time forms, every other layer the general one
-#define PD3_PV(RELU, WHOLE)                                                                                              \
-  do {                                                                                                                   \
-    const void* fn = reinterpret_cast<const void*>(conv3x3_winograd43_ppv_kernel<RELU, WHOLE>);                          \
-    const hipError_t e = pd3_max_dynamic_lds(fn, (int)lds);                                                              \
-    if (e != hipSuccess) return (int)e;                                                                                  \
-    conv3x3_winograd43_ppv_kernel<RELU, WHOLE><<<(unsigned)nwg, 512, lds, static_cast<hipStream_t>(stream)>>>(           \
-        v_pre, u_lane, bias, out, cin, cout, h, w, w_valid, relu, (int)ptiles, ipw);                                     \
-  } while (0)
-  if (!w4_whole(h, w, w_valid)) PD3_PV(-1, false);
-  else if (relu) PD3_PV(1, true);
-  else PD3_PV(0, true);
-#undef PD3_PV
-  return launch_status();
+  auto* kernel = !w4_whole(h, w, w_valid) ? conv3x3_winograd43_ppv_kernel<-1, false>
+                 : relu                   ? conv3x3_winograd43_ppv_kernel<1, true>
+                                          : conv3x3_winograd43_ppv_kernel<0, true>;
+  const int rc = launch_lds(kernel, (unsigned)nwg, 512, lds, static_cast<hipStream_t>(stream), v_pre, u_lane, bias, out, cin,
+                            cout, h, w, w_valid, relu, (int)ptiles, ipw);
+  return rc ? rc : launch_status();
 }

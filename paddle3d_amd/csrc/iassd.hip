@@ -320,13 +320,11 @@ int pd3_sa_msg_pool(const float* new_xyz, const float* xyz, const float* feature
   const int qpp = nsample <= 16 ? 4 : (nsample <= 32 ? 2 : 1);
   const int64_t passes = pd3::ceil_div(total, qpp);
   const int lds = kRows * ((c1 > c3 ? c1 : c3) + c2 + 8) * (int)sizeof(float);
-  hipError_t e = pd3::pd3_max_dynamic_lds((const void*)sa_msg_pool_kernel, lds);
-  if (e != hipSuccess) return (int)e;
   const dim3 grid((unsigned)(passes < kMaxBlocks ? passes : kMaxBlocks));
-  hipLaunchKernelGGL(sa_msg_pool_kernel, grid, dim3(kThreads), lds, (hipStream_t)stream, new_xyz, xyz, features_in,
-                     w_pos, scale1, shift1, w2, scale2, shift2, w3, scale3, shift3, total, m, n, c1, c2, c3,
-                     radius * radius, nsample, qpp, out, ld_out);
-  return pd3::launch_status();
+  const int rc = pd3::launch_lds(sa_msg_pool_kernel, grid, kThreads, lds, (hipStream_t)stream, new_xyz, xyz, features_in,
+                                 w_pos, scale1, shift1, w2, scale2, shift2, w3, scale3, shift3, total, m, n, c1, c2, c3,
+                                 radius * radius, nsample, qpp, out, ld_out);
+  return rc ? rc : pd3::launch_status();
 }
 
 int pd3_iassd_decode(const float* cls_preds, const float* box_preds, const float* centers, int64_t ld_centers,

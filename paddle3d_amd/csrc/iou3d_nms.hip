@@ -46,15 +46,9 @@ static int run_nms(const float* boxes, int n, float thresh, int32_t* keep, int32
   unsigned long long* mask = static_cast<unsigned long long*>(workspace);
   dim3 grid(cb, cb, 1);
   nms_mask_kernel<NORMAL><<<grid, 64, 0, s>>>(boxes, nullptr, n, n, cb, thresh, mask);
-  {
-    const size_t lds = nms_sweep_lds(n);
-    if (lds > 48 * 1024) {
-      hipError_t e = pd3_max_dynamic_lds(reinterpret_cast<const void*>(nms_sweep_kernel), (int)lds);
-      if (e != hipSuccess) return (int)e;
-    }
-    nms_sweep_kernel<<<1, kNmsSweepThreads, lds, s>>>(mask, nullptr, n, n, cb, keep, num_to_keep);
-  }
-  return launch_status();
+  const int rc = launch_lds(nms_sweep_kernel, 1, kNmsSweepThreads, nms_sweep_lds(n), s, mask, nullptr, n, n, cb, keep,
+                            num_to_keep);
+  return rc ? rc : launch_status();
 }
 
 }  // namespace pd3

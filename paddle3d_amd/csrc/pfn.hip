@@ -15,6 +15,7 @@
 #include "common.hpp"
 
 #include <algorithm>
+#include <type_traits>
 
 namespace pd3 {
 
@@ -939,12 +940,60 @@ __global__ __launch_bounds__(256) void voxel_mean_kernel(const float* __restrict
 
 using namespace pd3;
 
-static int pfn_dispatch(const float* voxels, const int32_t* num_points, const int32_t* coors,
-                        int64_t num_pillars, int max_points, int num_point_dim, int voxel_center_dims,
-                        float vx, float vy, float vz, float x_offset, float y_offset, float z_offset,
-                        const float* w1, const float* scale1, const float* shift1, int c1, const float* w2,
-                        const float* scale2, const float* shift2, int c2, float* out, int path,
-                        void* stream) {
+// The arguments both entry points share (the indexed one adds its own six fields)
+static PfnArgs pfn_args(const float* voxels, const int32_t* num_points, const int32_t* coors, int64_t num_pillars,
+                        int max_points, int num_point_dim, int voxel_center_dims, float vx, float vy, float vz,
+                        float x_offset, float y_offset, float z_offset, const float* w1, const float* scale1,
+                        const float* shift1, int c1, const float* w2, const float* scale2, const float* shift2, int c2,
+                        float* out) {
+  PfnArgs a{voxels, num_points, coors, num_pillars, max_points, num_point_dim, vx, vy, vz, x_offset, y_offset, z_offset,
+            voxel_center_dims, w1, scale1, shift1, c1, w2, scale2, shift2, w2 ? c2 : 0, out};
+  a.in_dim = num_point_dim + 3 + voxel_center_dims;
+  a.in_pad = (a.in_dim + 3) / 4 * 4;
+  return a;
+}
+
+// The run-time (num_point_dim in {4, 5}, voxel_center_dims in {2, 3}) as compile-time values:
+// f(std::integral_constant<int, D>, std::integral_constant<int, CD>)
+template <typename F>
+static int pfn_with_dims(const PfnArgs& a, F&& f) {
+  using std::integral_constant;
+  if (a.d == 4 && a.center_dims == 2) return f(integral_constant<int, 4>{}, integral_constant<int, 2>{});
+  if (a.d == 4) return f(integral_constant<int, 4>{}, integral_constant<int, 3>{});
+  if (a.center_dims == 2) return f(integral_constant<int, 5>{}, integral_constant<int, 2>{});
+  return f(integral_constant<int, 5>{}, integral_constant<int, 3>{});
+}
+
+// The packed two-layer kernel (PillarFeatureNet of the pillar models: Linear(<= 12, 32), Linear([32 | 32], 64), up to 32
+// points of 4 / 5 floats, kPkPillars pillars per chunk): the shapes it takes, the raw floats of a chunk in rows of 64 (NV),
+// its dynamic LDS and its grid
+static bool pfn_packed_ok(const PfnArgs& a) {
+  return a.w2 && a.c1 == 32 && a.c2 == 64 && a.p <= 32 && (a.d == 4 || a.d == 5) && a.in_dim <= 12 &&
+         kPkPillars * a.p * a.d <= 20 * 64;
+}
+static int pfn_packed_nv(const PfnArgs& a) { return (kPkPillars * a.p * a.d + 63) / 64 <= 13 ? 13 : 20; }
+static size_t pfn_packed_lds(const PfnArgs& a) {
+  const int rcap = (kPkPillars * a.p + 15) & ~15;
+  return ((size_t)4 * (pfn_packed_nv(a) * 64 + 16 * 34 + 16 * 68 + kPkPillars * 8 + rcap + 16 +
+                       (a.p * a.d >= 96 ? 0 : kPkPillars * 96)) + 32 * 64) * sizeof(float);
+}
+static unsigned pfn_packed_blocks(const PfnArgs& a) {
+  return (unsigned)std::min<int64_t>(ceil_div(ceil_div(a.m, (int64_t)kPkPillars), 4), 256 * 3);
+}
+
+// dynamic LDS of pfn_two_mfma_kernel<D, CD, C1, MAXP, LINE>
+constexpr size_t pfn_mfma_lds(int c1, int maxp, int line) {
+  return ((size_t)4 * (line + maxp * (c1 + 2) + c1 + 64 + 4 * 64) + (c1 == 32 ? c1 * 64 : 0)) * sizeof(float);
+}
+
+extern "C" int pd3_pillar_feature_net_path(const float* voxels, const int32_t* num_points,
+                                           const int32_t* coors, int64_t num_pillars, int max_points,
+                                           int num_point_dim, int voxel_center_dims, float vx, float vy,
+                                           float vz, float x_offset, float y_offset, float z_offset,
+                                           const float* w1, const float* scale1,
+                                           const float* shift1, int c1, const float* w2,
+                                           const float* scale2, const float* shift2, int c2, float* out,
+                                           int path, void* stream) {
   if (path < 0 || path > 2) return PD3_EINVAL;
   if (num_pillars < 0 || max_points <= 0 || num_point_dim < 3) return PD3_EINVAL;
   if (voxel_center_dims != 2 && voxel_center_dims != 3) return PD3_EINVAL;
@@ -952,55 +1001,22 @@ static int pfn_dispatch(const float* voxels, const int32_t* num_points, const in
   if (!voxels || !num_points || !coors || !w1 || !scale1 || !shift1 || !out) return PD3_EINVAL;
   if (c1 <= 0 || c1 > 64 || (c1 % 4) != 0) return PD3_EUNSUPPORTED;
   if (w2 && (!scale2 || !shift2 || c2 <= 0 || c2 > 64)) return PD3_EUNSUPPORTED;
-  PfnArgs a;
-  a.voxels = voxels;
-  a.num_points = num_points;
-  a.coors = coors;
-  a.m = num_pillars;
-  a.p = max_points;
-  a.d = num_point_dim;
-  a.vx = vx;
-  a.vy = vy;
-  a.vz = vz;
-  a.x_off = x_offset;
-  a.y_off = y_offset;
-  a.z_off = z_offset;
-  a.center_dims = voxel_center_dims;
-  a.w1 = w1;
-  a.scale1 = scale1;
-  a.shift1 = shift1;
-  a.c1 = c1;
-  a.w2 = w2;
-  a.scale2 = scale2;
-  a.shift2 = shift2;
-  a.c2 = w2 ? c2 : 0;
-  a.out = out;
-  a.in_dim = num_point_dim + 3 + voxel_center_dims;
-  a.in_pad = (a.in_dim + 3) / 4 * 4;
+  const PfnArgs a = pfn_args(voxels, num_points, coors, num_pillars, max_points, num_point_dim, voxel_center_dims, vx, vy,
+                             vz, x_offset, y_offset, z_offset, w1, scale1, shift1, c1, w2, scale2, shift2, c2, out);
   // xs must also be able to hold c1 maxima (see mx_store)
   if (max_points * a.in_pad < c1) return PD3_EUNSUPPORTED;
   hipStream_t s = static_cast<hipStream_t>(stream);
+  int rc = 0;
   if (!w2 && c1 == 64 && max_points * num_point_dim <= 128 && (num_point_dim == 4 || num_point_dim == 5)) {
     const unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(num_pillars, 4), 256 * 16);
-    if (num_point_dim == 4 && voxel_center_dims == 2) pfn_single64_kernel<4, 2><<<blocks, 256, 0, s>>>(a);
-    else if (num_point_dim == 4) pfn_single64_kernel<4, 3><<<blocks, 256, 0, s>>>(a);
-    else if (voxel_center_dims == 2) pfn_single64_kernel<5, 2><<<blocks, 256, 0, s>>>(a);
-    else pfn_single64_kernel<5, 3><<<blocks, 256, 0, s>>>(a);
+    pfn_with_dims(a, [&](auto d, auto cd) {
+      pfn_single64_kernel<decltype(d)::value, decltype(cd)::value><<<blocks, 256, 0, s>>>(a);
+      return 0;
+    });
     return launch_status();
   }
-#define PD3_PFN_MFMA(DD, CDV, C1V, MAXPV, LINEV)                                                                \
-  do {                                                                                                        \
-    constexpr size_t lds_ = ((size_t)4 * (LINEV + MAXPV * (C1V + 2) + C1V + 64 + 4 * 64) +                     \
-                             (C1V == 32 ? C1V * 64 : 0)) * sizeof(float);                                      \
-    if (lds_ > 48 * 1024) {                                                                                    \
-      hipError_t e_ = pd3_max_dynamic_lds(reinterpret_cast<const void*>(pfn_two_mfma_kernel<DD, CDV, C1V, MAXPV, LINEV>), (int)lds_);              \
-      if (e_ != hipSuccess) return (int)e_;                                                                    \
-    }                                                                                                          \
-    pfn_two_mfma_kernel<DD, CDV, C1V, MAXPV, LINEV><<<blocks, 256, lds_, s>>>(a);                              \
-  } while (0)
   // packed form (path 0 picks it where it applies; path 1 = the per-pillar forms below; path 2 = this or nothing)
-  const bool packed_ok = w2 && c1 == 32 && c2 == 64 && max_points <= 32 && (num_point_dim == 4 || num_point_dim == 5) &&
-                         a.in_dim <= 12 && kPkPillars * max_points * num_point_dim <= 20 * 64;
+  const bool packed_ok = pfn_packed_ok(a);
   // the same form for HardVFE's widths (Linear(10, 64), Linear([64 | 64], 64), up to 64 points of 4 floats): four
   // pillars per chunk
   const bool packed64_ok = w2 && c1 == 64 && c2 == 64 && max_points <= 64 && num_point_dim == 4 &&
@@ -1015,71 +1031,41 @@ static int pfn_dispatch(const float* voxels, const int32_t* num_points, const in
     const int rcap = (kPc * max_points + 15) & ~15;
     const size_t lds = ((size_t)4 * (kNv * 64 + 16 * 68 + 16 * 68 + kPc * 8 + rcap + 16 +
                                      (max_points * num_point_dim >= kC1 + 64 ? 0 : kPc * (kC1 + 64)))) * sizeof(float);
-    if (lds > 48 * 1024) {
-      hipError_t e_ = pd3_max_dynamic_lds(reinterpret_cast<const void*>(pfn_packed_kernel<4, 3, kNv, kC1, kPc, true>), (int)lds);
-      if (e_ != hipSuccess) return (int)e_;
-    }
-    pfn_packed_kernel<4, 3, kNv, kC1, kPc, true><<<blocks, 256, lds, s>>>(a);
-    return launch_status();
+    rc = launch_lds(pfn_packed_kernel<4, 3, kNv, kC1, kPc, true>, blocks, 256, lds, s, a);
+    return rc ? rc : launch_status();
   }
   if (packed_ok && path != 1) {
-    const int64_t nchunks = ceil_div(num_pillars, (int64_t)kPkPillars);
-    const unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(nchunks, 4), 256 * 3);
-    const int nv = (kPkPillars * max_points * num_point_dim + 63) / 64 <= 13 ? 13 : 20;
-    const int rcap = (kPkPillars * max_points + 15) & ~15;
-    const size_t lds = ((size_t)4 * (nv * 64 + 16 * 34 + 16 * 68 + kPkPillars * 8 + rcap + 16 +
-                                     (max_points * num_point_dim >= 96 ? 0 : kPkPillars * 96)) + 32 * 64) * sizeof(float);
-#define PD3_PFN_PACKED(DD, CDV, NVV)                                                                               \
-  do {                                                                                                            \
-    if (lds > 48 * 1024) {                                                                                        \
-      hipError_t e_ = pd3_max_dynamic_lds(reinterpret_cast<const void*>(pfn_packed_kernel<DD, CDV, NVV>), (int)lds);                  \
-      if (e_ != hipSuccess) return (int)e_;                                                                       \
-    }                                                                                                             \
-    pfn_packed_kernel<DD, CDV, NVV><<<blocks, 256, lds, s>>>(a);                                                  \
-  } while (0)
-    if (nv == 13) {
-      if (num_point_dim == 4 && voxel_center_dims == 2) PD3_PFN_PACKED(4, 2, 13);
-      else if (num_point_dim == 4) PD3_PFN_PACKED(4, 3, 13);
-      else if (voxel_center_dims == 2) PD3_PFN_PACKED(5, 2, 13);
-      else PD3_PFN_PACKED(5, 3, 13);
-    } else {
-      if (num_point_dim == 4 && voxel_center_dims == 2) PD3_PFN_PACKED(4, 2, 20);
-      else if (num_point_dim == 4) PD3_PFN_PACKED(4, 3, 20);
-      else if (voxel_center_dims == 2) PD3_PFN_PACKED(5, 2, 20);
-      else PD3_PFN_PACKED(5, 3, 20);
-    }
-#undef PD3_PFN_PACKED
-    return launch_status();
+    rc = pfn_with_dims(a, [&](auto d, auto cd) {
+      constexpr int kD = decltype(d)::value, kCd = decltype(cd)::value;
+      return launch_lds(pfn_packed_nv(a) == 13 ? pfn_packed_kernel<kD, kCd, 13> : pfn_packed_kernel<kD, kCd, 20>,
+                        pfn_packed_blocks(a), 256, pfn_packed_lds(a), s, a);
+    });
+    return rc ? rc : launch_status();
   }
   if (w2 && c1 == 32 && c2 == 64 && max_points * num_point_dim <= 128 && max_points <= 32 &&
       (num_point_dim == 4 || num_point_dim == 5) && a.in_dim <= 12) {
     const unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(num_pillars, 4), 256 * 8);
-    if (num_point_dim == 4 && voxel_center_dims == 2) PD3_PFN_MFMA(4, 2, 32, 32, 128);
-    else if (num_point_dim == 4) PD3_PFN_MFMA(4, 3, 32, 32, 128);
-    else if (voxel_center_dims == 2) PD3_PFN_MFMA(5, 2, 32, 32, 128);
-    else PD3_PFN_MFMA(5, 3, 32, 32, 128);
-    return launch_status();
+    rc = pfn_with_dims(a, [&](auto d, auto cd) {
+      return launch_lds(pfn_two_mfma_kernel<decltype(d)::value, decltype(cd)::value, 32, 32, 128>, blocks, 256,
+                        pfn_mfma_lds(32, 32, 128), s, a);
+    });
+    return rc ? rc : launch_status();
   }
   if (w2 && c1 == 64 && c2 == 64 && max_points * num_point_dim <= 256 && max_points <= 64 &&
       num_point_dim == 4 && voxel_center_dims == 3 && a.in_dim <= 12) {  // HardVFE (BEVFusion LiDAR stream)
     const unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(num_pillars, 4), 256 * 8);
-    PD3_PFN_MFMA(4, 3, 64, 64, 256);
-    return launch_status();
+    rc = launch_lds(pfn_two_mfma_kernel<4, 3, 64, 64, 256>, blocks, 256, pfn_mfma_lds(64, 64, 256), s, a);
+    return rc ? rc : launch_status();
   }
-#undef PD3_PFN_MFMA
   const size_t w_floats = (size_t)a.in_pad * c1 + (w2 ? (size_t)2 * c1 * c2 : 0);
   const size_t wave_floats = (size_t)max_points * a.in_pad + (size_t)max_points * c1;
   int waves = kPfnMaxWaves;
   while (waves > 1 && (w_floats + waves * wave_floats) * sizeof(float) > 160 * 1024) waves >>= 1;
   const size_t bytes = (w_floats + waves * wave_floats) * sizeof(float);
   if (bytes > 160 * 1024) return PD3_EUNSUPPORTED;
-  if (bytes > 48 * 1024) {
-    hipError_t e = pd3_max_dynamic_lds(reinterpret_cast<const void*>(pfn_kernel), (int)bytes);
-    if (e != hipSuccess) return (int)e;
-  }
   const int64_t blocks = std::min<int64_t>(ceil_div(num_pillars, waves), 256 * 8);
-  pfn_kernel<<<(unsigned)blocks, waves * 64, bytes, s>>>(a);
-  return launch_status();
+  rc = launch_lds(pfn_kernel, (unsigned)blocks, waves * 64, bytes, s, a);
+  return rc ? rc : launch_status();
 }
 
 extern "C" int pd3_pillar_feature_net_indexed(const float* points, int64_t points_per_frame, const int32_t* vox_span,
@@ -1097,78 +1083,30 @@ extern "C" int pd3_pillar_feature_net_indexed(const float* points, int64_t point
   if (num_pillars == 0) return 0;
   if (!points || !vox_span || !point_list || !coors || !w1 || !scale1 || !shift1 || !w2 || !scale2 || !shift2 || !out)
     return PD3_EINVAL;
-  const int in_dim = num_point_dim + 3 + voxel_center_dims;
-  // the shapes of the packed two-layer kernel (PillarFeatureNet of the pillar models), whole chunks per frame, grid
-  // coordinates that fit 16 bits, pillar ids the fp32 frame lookup is exact for
-  if (!(c1 == 32 && c2 == 64 && max_points <= 32 && (num_point_dim == 4 || num_point_dim == 5) && in_dim <= 12 &&
-        kPkPillars * max_points * num_point_dim <= 20 * 64 && pillars_per_frame % kPkPillars == 0 &&
-        num_pillars % pillars_per_frame == 0 && num_pillars < ((int64_t)1 << 22)))
+  PfnArgs a = pfn_args(nullptr, nullptr, coors, num_pillars, max_points, num_point_dim, voxel_center_dims, vx, vy, vz,
+                       x_offset, y_offset, z_offset, w1, scale1, shift1, c1, w2, scale2, shift2, c2, out);
+  // the shapes of the packed kernel, whole chunks per frame, grid coordinates that fit 16 bits, pillar ids the fp32 frame
+  // lookup is exact for
+  if (!(pfn_packed_ok(a) && pillars_per_frame % kPkPillars == 0 && num_pillars % pillars_per_frame == 0 &&
+        num_pillars < ((int64_t)1 << 22)))
     return PD3_EUNSUPPORTED;
-  PfnArgs a{};
-  a.voxels = nullptr;
-  a.num_points = nullptr;
-  a.coors = coors;
-  a.m = num_pillars;
-  a.p = max_points;
-  a.d = num_point_dim;
-  a.vx = vx;
-  a.vy = vy;
-  a.vz = vz;
-  a.x_off = x_offset;
-  a.y_off = y_offset;
-  a.z_off = z_offset;
-  a.center_dims = voxel_center_dims;
-  a.w1 = w1;
-  a.scale1 = scale1;
-  a.shift1 = shift1;
-  a.c1 = c1;
-  a.w2 = w2;
-  a.scale2 = scale2;
-  a.shift2 = shift2;
-  a.c2 = c2;
-  a.out = out;
-  a.in_dim = in_dim;
-  a.in_pad = (in_dim + 3) / 4 * 4;
   a.points = points;
   a.n_pts = points_per_frame;
   a.span = reinterpret_cast<const uint2*>(vox_span);
   a.plist = reinterpret_cast<const uint32_t*>(point_list);
   a.list_stride = list_stride;
   a.vper = pillars_per_frame;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int64_t nchunks = ceil_div(num_pillars, (int64_t)kPkPillars);
-  const unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(nchunks, 4), 256 * 3);
-  const int nv = (kPkPillars * max_points * num_point_dim + 63) / 64 <= 13 ? 13 : 20;
-  const int rcap = (kPkPillars * max_points + 15) & ~15;
-  const size_t lds = ((size_t)4 * (nv * 64 + 16 * 34 + 16 * 68 + kPkPillars * 8 + rcap + 16 +
-                                   (max_points * num_point_dim >= 96 ? 0 : kPkPillars * 96)) + 32 * 64) * sizeof(float);
-#define PD3_PFN_INDEXED_N(DD, CDV, NVV, NS)                                                                           \
-  do {                                                                                                               \
-    if (lds > 48 * 1024) {                                                                                           \
-      hipError_t e_ = pd3_max_dynamic_lds(reinterpret_cast<const void*>(pfn_packed_kernel<DD, CDV, NVV, 32, kPkPillars, false, true, NS>), (int)lds);                                                     \
-      if (e_ != hipSuccess) return (int)e_;                                                                          \
-    }                                                                                                                \
-    pfn_packed_kernel<DD, CDV, NVV, 32, kPkPillars, false, true, NS><<<blocks, 256, lds, s>>>(a);                    \
-  } while (0)
-#define PD3_PFN_INDEXED(DD, CDV, NVV)                                                                                 \
-  do {                                                                                                               \
-    if (kPkPillars * max_points <= 192) PD3_PFN_INDEXED_N(DD, CDV, NVV, 3);                                          \
-    else PD3_PFN_INDEXED_N(DD, CDV, NVV, 4);                                                                         \
-  } while (0)
-  if (nv == 13) {
-    if (num_point_dim == 4 && voxel_center_dims == 2) PD3_PFN_INDEXED(4, 2, 13);
-    else if (num_point_dim == 4) PD3_PFN_INDEXED(4, 3, 13);
-    else if (voxel_center_dims == 2) PD3_PFN_INDEXED(5, 2, 13);
-    else PD3_PFN_INDEXED(5, 3, 13);
-  } else {
-    if (num_point_dim == 4 && voxel_center_dims == 2) PD3_PFN_INDEXED(4, 2, 20);
-    else if (num_point_dim == 4) PD3_PFN_INDEXED(4, 3, 20);
-    else if (voxel_center_dims == 2) PD3_PFN_INDEXED(5, 2, 20);
-    else PD3_PFN_INDEXED(5, 3, 20);
-  }
-#undef PD3_PFN_INDEXED
-#undef PD3_PFN_INDEXED_N
-  return launch_status();
+  const bool nv13 = pfn_packed_nv(a) == 13, ns3 = kPkPillars * max_points <= 192;
+  const int rc = pfn_with_dims(a, [&](auto d, auto cd) {
+    constexpr int kD = decltype(d)::value, kCd = decltype(cd)::value;
+    return launch_lds(
+        nv13 ? (ns3 ? pfn_packed_kernel<kD, kCd, 13, 32, kPkPillars, false, true, 3>
+                    : pfn_packed_kernel<kD, kCd, 13, 32, kPkPillars, false, true, 4>)
+             : (ns3 ? pfn_packed_kernel<kD, kCd, 20, 32, kPkPillars, false, true, 3>
+                    : pfn_packed_kernel<kD, kCd, 20, 32, kPkPillars, false, true, 4>),
+        pfn_packed_blocks(a), 256, pfn_packed_lds(a), static_cast<hipStream_t>(stream), a);
+  });
+  return rc ? rc : launch_status();
 }
 
 extern "C" int pd3_pillar_feature_net(const float* voxels, const int32_t* num_points,
@@ -1179,22 +1117,9 @@ extern "C" int pd3_pillar_feature_net(const float* voxels, const int32_t* num_po
                                       const float* shift1, int c1, const float* w2,
                                       const float* scale2, const float* shift2, int c2, float* out,
                                       void* stream) {
-  return pfn_dispatch(voxels, num_points, coors, num_pillars, max_points, num_point_dim, voxel_center_dims, vx, vy,
-                      vz, x_offset, y_offset, z_offset, w1, scale1, shift1, c1, w2, scale2, shift2, c2, out, 0,
-                      stream);
-}
-
-extern "C" int pd3_pillar_feature_net_path(const float* voxels, const int32_t* num_points,
-                                           const int32_t* coors, int64_t num_pillars, int max_points,
-                                           int num_point_dim, int voxel_center_dims, float vx, float vy,
-                                           float vz, float x_offset, float y_offset, float z_offset,
-                                           const float* w1, const float* scale1,
-                                           const float* shift1, int c1, const float* w2,
-                                           const float* scale2, const float* shift2, int c2, float* out,
-                                           int path, void* stream) {
-  return pfn_dispatch(voxels, num_points, coors, num_pillars, max_points, num_point_dim, voxel_center_dims, vx, vy,
-                      vz, x_offset, y_offset, z_offset, w1, scale1, shift1, c1, w2, scale2, shift2, c2, out, path,
-                      stream);
+  return pd3_pillar_feature_net_path(voxels, num_points, coors, num_pillars, max_points, num_point_dim,
+                                     voxel_center_dims, vx, vy, vz, x_offset, y_offset, z_offset, w1, scale1, shift1, c1,
+                                     w2, scale2, shift2, c2, out, 0, stream);
 }
 
 extern "C" int pd3_voxel_mean(const float* voxels, const int32_t* num_points, int64_t num_voxels,

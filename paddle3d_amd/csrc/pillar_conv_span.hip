@@ -311,8 +311,6 @@ extern "C" int pd3_pillar_conv_span_x3(const float* feats, int n_in, const int32
                cout, relu ? 1 : 0, (int)spans};
   const int nh = cout / kPsCh;
   const unsigned grid = (unsigned)(spans < kPsGrid / nh ? spans : kPsGrid / nh) * nh;
-  hipError_t e = pd3_max_dynamic_lds(reinterpret_cast<const void*>(pc_span_x3_kernel), (int)kPsLds);
-  if (e != hipSuccess) return (int)e;
-  pc_span_x3_kernel<<<grid, kPsCells, kPsLds, static_cast<hipStream_t>(stream)>>>(a);
-  return launch_status();
+  const int rc = launch_lds(pc_span_x3_kernel, grid, kPsCells, kPsLds, static_cast<hipStream_t>(stream), a);
+  return rc ? rc : launch_status();
 }

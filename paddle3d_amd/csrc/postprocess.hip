@@ -573,6 +573,7 @@ static int cp_postprocess_impl(
   for (int t = 0; t < num_tasks; ++t) byte_classes = byte_classes && hm_channels[t] <= 256;
   if (hw <= kTopkMaxHw && cap <= kTopkMaxK && byte_classes && selection == 0) {
     const size_t lds = cp_topk_lds(hw);
+    // (hand-written: the cap reserved is the largest map's, not this launch's own size)
     e = pd3_max_dynamic_lds(reinterpret_cast<const void*>(cp_topk_kernel), (int)cp_topk_lds(kTopkMaxHw));
     if (e != hipSuccess) return (int)e;
     cp_topk_kernel<<<sets, kTopkThreads, lds, s>>>(h, c, w.counts, w.pool.counts, cap, rows,
@@ -588,14 +589,9 @@ static int cp_postprocess_impl(
     cp_nms_boxes_kernel<<<bgrid, 256, 0, s>>>(h, c, where ? w.vals_b : w.vals_a, w.counts, cap, rows);
   }
   nms_enqueue_mask_pooled(w.pre, w.counts, sets, cap, cb, nms_iou_threshold, w.mask, w.pool, s);
-  {
-    const size_t lds = nms_sweep_lds(cap);
-    if (lds > 48 * 1024) {
-      e = pd3_max_dynamic_lds(reinterpret_cast<const void*>(nms_sweep_kernel), (int)lds);
-      if (e != hipSuccess) return (int)e;
-    }
-    nms_sweep_kernel<<<sets, kNmsSweepThreads, lds, s>>>(w.mask, w.counts, 0, cap, cb, w.keep, w.nkeep);
-  }
+  if (const int rc = launch_lds(nms_sweep_kernel, sets, kNmsSweepThreads, nms_sweep_lds(cap), s, w.mask, w.counts, 0, cap,
+                                cb, w.keep, w.nkeep))
+    return rc;
   cp_output_kernel<<<dim3(num_tasks, batch), 256, 0, s>>>(w.boxes, w.scores, w.labels, w.counts, w.keep, w.nkeep, h,
                                      num_tasks, hw, c.dims, cap, nms_pre_max_size, nms_post_max_size, out_bboxes,
                                      out_scores, out_labels, out_count, out_records, max_per_img);

@@ -441,12 +441,9 @@ int pd3_class_agnostic_nms(const float* box_preds, const float* cls_preds, int b
     can_boxes_kernel<<<dim3((cap + 255) / 256, batch), 256, 0, s>>>(box_preds, sidx, w.counts, (int)a, cap, w.pre,
                                                                     w.pool.xyr);
     nms_enqueue_mask_pooled(w.pre, w.counts, batch, cap, cb, nms_thresh, w.mask, w.pool, s);
-    const size_t lds = nms_sweep_lds(cap);
-    if (lds > 48 * 1024) {
-      e = pd3_max_dynamic_lds(reinterpret_cast<const void*>(nms_sweep_kernel), (int)lds);
-      if (e != hipSuccess) return (int)e;
-    }
-    nms_sweep_kernel<<<batch, kNmsSweepThreads, lds, s>>>(w.mask, w.counts, 0, cap, cb, w.keep, w.nkeep);
+    if (const int rc = launch_lds(nms_sweep_kernel, batch, kNmsSweepThreads, nms_sweep_lds(cap), s, w.mask, w.counts, 0, cap,
+                                  cb, w.keep, w.nkeep))
+      return rc;
   }
   can_output_kernel<<<batch, 256, 0, s>>>(box_preds, w.scores, w.labels, labels, sidx, w.counts, w.keep, w.nkeep,
                                           (int)a, cap, nms_post_maxsize, score_thresh == score_thresh ? 1 : 0,

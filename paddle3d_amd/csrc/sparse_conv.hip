@@ -1279,7 +1279,7 @@ extern "C" int pd3_sparse_conv3d_features_ordered(const float* in_feats, const i
   SpGemmArgs a{in_feats, nbr, weight, bias, scale, shift, residual, out, n_out, n_out_cap,
                kernel_volume, cin, cout, relu ? 1 : 0, order};
   hipStream_t s = static_cast<hipStream_t>(stream);
-  hipError_t e;
+  int rc;
   if (cin % 16 == 0 && kernel_volume <= kSg2MaxK && (cout == 16 || cout == 32 || cout == 64 || cout == 128) &&
       reinterpret_cast<uintptr_t>(weight) % 16 == 0 && reinterpret_cast<uintptr_t>(in_feats) % 16 == 0) {
     // the encoder's shapes: 128-row tiles, A operand straight from global memory
@@ -1287,29 +1287,20 @@ extern "C" int pd3_sparse_conv3d_features_ordered(const float* in_feats, const i
     const size_t lds = (size_t)2 * 64 * (nb * t + 4) * sizeof(float) +
                        ((size_t)kSg2Rows * kernel_volume + 16 + kSg2Rows) * sizeof(int);
     const unsigned grid = sp_window_grid(ceil_div(n_out_cap, kSg2Rows), 8192 / kSg2Rows);
-#define PD3_SP_ROWS(NBV, TV)                                                                      \
-  do {                                                                                            \
-    if (lds > 48 * 1024) {                                                                        \
-      e = pd3_max_dynamic_lds(reinterpret_cast<const void*>(sp_gemm_rows_kernel<NBV, TV>), (int)lds);              \
-      if (e != hipSuccess) return (int)e;                                                         \
-    }                                                                                             \
-    sp_gemm_rows_kernel<NBV, TV><<<grid, 256, lds, s>>>(a);                                       \
-  } while (0)
+    void (*kernel)(SpGemmArgs);
     switch (nb * 16 + t) {
-      case 1 * 16 + 4: PD3_SP_ROWS(1, 4); break;
-      case 1 * 16 + 8: PD3_SP_ROWS(1, 8); break;
-      case 2 * 16 + 4: PD3_SP_ROWS(2, 4); break;
-      case 2 * 16 + 8: PD3_SP_ROWS(2, 8); break;
-      case 4 * 16 + 4: PD3_SP_ROWS(4, 4); break;
-      case 4 * 16 + 8: PD3_SP_ROWS(4, 8); break;
-      case 8 * 16 + 4: PD3_SP_ROWS(8, 4); break;
-      default: PD3_SP_ROWS(8, 8); break;
+      case 1 * 16 + 4: kernel = sp_gemm_rows_kernel<1, 4>; break;
+      case 1 * 16 + 8: kernel = sp_gemm_rows_kernel<1, 8>; break;
+      case 2 * 16 + 4: kernel = sp_gemm_rows_kernel<2, 4>; break;
+      case 2 * 16 + 8: kernel = sp_gemm_rows_kernel<2, 8>; break;
+      case 4 * 16 + 4: kernel = sp_gemm_rows_kernel<4, 4>; break;
+      case 4 * 16 + 8: kernel = sp_gemm_rows_kernel<4, 8>; break;
+      case 8 * 16 + 4: kernel = sp_gemm_rows_kernel<8, 4>; break;
+      default: kernel = sp_gemm_rows_kernel<8, 8>; break;
     }
-#undef PD3_SP_ROWS
-    return launch_status();
-  }
-  if (cout % 16 == 0 && (reinterpret_cast<uintptr_t>(weight) % 16 == 0) &&
-      (cin % 4 != 0 || reinterpret_cast<uintptr_t>(in_feats) % 16 == 0)) {
+    rc = launch_lds(kernel, grid, 256, lds, s, a);
+  } else if ((cout == 16 || cout == 32 || cout == 64 || cout == 128) && reinterpret_cast<uintptr_t>(weight) % 16 == 0 &&
+             (cin % 4 != 0 || reinterpret_cast<uintptr_t>(in_feats) % 16 == 0)) {
     // matrix-core path, any cin (the encoder's input layer: cin = 5)
     const int cin_pad = (cin + 3) / 4 * 4;
     const int astride = ((cin_pad - 2 + 15) / 16) * 16 + 2;
@@ -1317,44 +1308,21 @@ extern "C" int pd3_sparse_conv3d_features_ordered(const float* in_feats, const i
     const size_t lds = ((size_t)4 * 16 * astride + (size_t)kSpChunk * wstride) * sizeof(float) +
                        kSpTile * sizeof(int);
     const unsigned grid = (unsigned)ceil_div(n_out_cap, kSpTile);
-#define PD3_SP_MFMA(NBV)                                                                          \
-  do {                                                                                            \
-    if (lds > 48 * 1024) {                                                                        \
-      e = pd3_max_dynamic_lds(reinterpret_cast<const void*>(sp_gemm_mfma_kernel<NBV>), (int)lds);              \
-      if (e != hipSuccess) return (int)e;                                                         \
-    }                                                                                             \
-    sp_gemm_mfma_kernel<NBV><<<grid, 256, lds, s>>>(a, cin_pad, astride, wstride);               \
-  } while (0)
+    void (*kernel)(SpGemmArgs, int, int, int);
     switch (cout / 16) {
-      case 1: PD3_SP_MFMA(1); break;
-      case 2: PD3_SP_MFMA(2); break;
-      case 4: PD3_SP_MFMA(4); break;
-      case 8: PD3_SP_MFMA(8); break;
-      default: goto valu_path;
+      case 1: kernel = sp_gemm_mfma_kernel<1>; break;
+      case 2: kernel = sp_gemm_mfma_kernel<2>; break;
+      case 4: kernel = sp_gemm_mfma_kernel<4>; break;
+      default: kernel = sp_gemm_mfma_kernel<8>; break;
     }
-#undef PD3_SP_MFMA
-    return launch_status();
-  }
-valu_path:
-  {
+    rc = launch_lds(kernel, grid, 256, lds, s, a, cin_pad, astride, wstride);
+  } else {
     const size_t lds = ((size_t)cin * cout + (size_t)kSpRows * cin) * sizeof(float) + kSpRows * sizeof(int);
     if (lds > 160 * 1024) return PD3_EUNSUPPORTED;
     const unsigned grid = (unsigned)ceil_div(n_out_cap, kSpRows);
-    if (cout <= 64) {
-      if (lds > 48 * 1024) {
-        e = pd3_max_dynamic_lds(reinterpret_cast<const void*>(sp_gather_gemm_kernel<1>), (int)lds);
-        if (e != hipSuccess) return (int)e;
-      }
-      sp_gather_gemm_kernel<1><<<grid, 256, lds, s>>>(a);
-    } else {
-      if (lds > 48 * 1024) {
-        e = pd3_max_dynamic_lds(reinterpret_cast<const void*>(sp_gather_gemm_kernel<2>), (int)lds);
-        if (e != hipSuccess) return (int)e;
-      }
-      sp_gather_gemm_kernel<2><<<grid, 256, lds, s>>>(a);
-    }
+    rc = launch_lds(cout <= 64 ? sp_gather_gemm_kernel<1> : sp_gather_gemm_kernel<2>, grid, 256, lds, s, a);
   }
-  return launch_status();
+  return rc ? rc : launch_status();
 }
 
 extern "C" int64_t pd3_sparse_tile_order_entries(int n_out_cap) {
@@ -1367,13 +1335,11 @@ extern "C" int pd3_sparse_tile_order(const int32_t* nbr, const int32_t* n_out, i
   if (!nbr || !order || n_out_cap <= 0 || kernel_volume <= 0 || kernel_volume > 31) return PD3_EINVAL;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const size_t lds = (size_t)2 * kSpWindow * sizeof(uint32_t);
-  // raised on every launch like every other large-LDS kernel of the library (a host-side table write): a process-wide
-  // flag would be unsynchronised and, if the attribute is kept per device, wrong for a second GPU in the process
-  const hipError_t e = pd3_max_dynamic_lds(reinterpret_cast<const void*>(sp_tile_order_kernel), (int)lds);
-  if (e != hipSuccess) return (int)e;
-  sp_tile_order_kernel<<<(unsigned)ceil_div(n_out_cap, kSpWindow), kSpOrderThreads, lds, s>>>(
-      nbr, n_out, n_out_cap, kernel_volume, order);
-  return launch_status();
+  // (64 KiB: the cap is kept per kernel and device by pd3_max_dynamic_lds -- a process-wide flag here would be
+  // unsynchronised and wrong for a second GPU in the process)
+  const int rc = launch_lds(sp_tile_order_kernel, (unsigned)ceil_div(n_out_cap, kSpWindow), kSpOrderThreads, lds, s, nbr,
+                            n_out, n_out_cap, kernel_volume, order);
+  return rc ? rc : launch_status();
 }
 
 extern "C" int pd3_sparse_to_dense(const float* feats, const int32_t* coords, const int32_t* n,

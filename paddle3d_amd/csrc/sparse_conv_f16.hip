@@ -327,27 +327,19 @@ extern "C" int pd3_gather_gemm_f16(const void* in_feats_f16, const int32_t* nbr,
   const size_t lds = (size_t)2 * cout * (kc + 8) * sizeof(_Float16) +
                      ((size_t)kSfRows * kernel_volume + 16 + kSfRows) * sizeof(int);
   const unsigned grid = sp_window_grid(ceil_div(n_out_cap, kSfRows), 8192 / kSfRows);
-  hipError_t e;
-#define PD3_SF(NCV, KCV)                                                                           \
-  do {                                                                                             \
-    if (lds > 48 * 1024) {                                                                         \
-      e = pd3_max_dynamic_lds(reinterpret_cast<const void*>(sp_gemm_rows_f16_kernel<NCV, KCV>), (int)lds);               \
-      if (e != hipSuccess) return (int)e;                                                          \
-    }                                                                                              \
-    sp_gemm_rows_f16_kernel<NCV, KCV><<<grid, 256, lds, s>>>(a);                                   \
-  } while (0)
+  void (*kernel)(SpGemmF16Args);
   switch (nc * 100 + kc) {
-    case 116: PD3_SF(1, 16); break;
-    case 132: PD3_SF(1, 32); break;
-    case 164: PD3_SF(1, 64); break;
-    case 216: PD3_SF(2, 16); break;
-    case 232: PD3_SF(2, 32); break;
-    case 264: PD3_SF(2, 64); break;
-    case 416: PD3_SF(4, 16); break;
-    case 432: PD3_SF(4, 32); break;
-    case 464: PD3_SF(4, 64); break;
+    case 116: kernel = sp_gemm_rows_f16_kernel<1, 16>; break;
+    case 132: kernel = sp_gemm_rows_f16_kernel<1, 32>; break;
+    case 164: kernel = sp_gemm_rows_f16_kernel<1, 64>; break;
+    case 216: kernel = sp_gemm_rows_f16_kernel<2, 16>; break;
+    case 232: kernel = sp_gemm_rows_f16_kernel<2, 32>; break;
+    case 264: kernel = sp_gemm_rows_f16_kernel<2, 64>; break;
+    case 416: kernel = sp_gemm_rows_f16_kernel<4, 16>; break;
+    case 432: kernel = sp_gemm_rows_f16_kernel<4, 32>; break;
+    case 464: kernel = sp_gemm_rows_f16_kernel<4, 64>; break;
     default: return PD3_EUNSUPPORTED;
   }
-#undef PD3_SF
-  return launch_status();
+  const int rc = launch_lds(kernel, grid, 256, lds, s, a);
+  return rc ? rc : launch_status();
 }

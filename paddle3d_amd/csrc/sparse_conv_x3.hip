@@ -410,24 +410,17 @@ extern "C" int pd3_sparse_conv3d_features_bf16x3(const float* in_feats, const in
   const size_t lds = (size_t)2 * 3 * cout * (kc + 8) * sizeof(__bf16) +
                      ((size_t)kSxRows * kernel_volume + 16 + kSxRows) * sizeof(int);
   const unsigned grid = sp_window_grid(ceil_div(n_out_cap, kSxRows), 8192 / kSxRows);
-  hipError_t e;
-#define PD3_SX(NCV, KCV, RBV)                                                                        \
-  do {                                                                                               \
-    if (lds > 48 * 1024) {                                                                           \
-      e = pd3_max_dynamic_lds(reinterpret_cast<const void*>(sp_gemm_rows_x3_kernel<NCV, KCV, RBV>), (int)lds);                 \
-      if (e != hipSuccess) return (int)e;                                                            \
-    }                                                                                                \
-    sp_gemm_rows_x3_kernel<NCV, KCV, RBV><<<grid, 64 * (8 / RBV), lds, s>>>(a);                      \
-  } while (0)
+  const int rb = nc == 4 ? 1 : 2;  // RB of the instantiation below: 8 / RB waves per workgroup
+  void (*kernel)(SpGemmX3Args);
   switch (nc * 100 + kc) {
-    case 116: PD3_SX(1, 16, 2); break;
-    case 132: PD3_SX(1, 32, 2); break;
-    case 216: PD3_SX(2, 16, 2); break;
-    case 232: PD3_SX(2, 32, 2); break;
-    case 416: PD3_SX(4, 16, 1); break;
-    case 432: PD3_SX(4, 32, 1); break;
+    case 116: kernel = sp_gemm_rows_x3_kernel<1, 16, 2>; break;
+    case 132: kernel = sp_gemm_rows_x3_kernel<1, 32, 2>; break;
+    case 216: kernel = sp_gemm_rows_x3_kernel<2, 16, 2>; break;
+    case 232: kernel = sp_gemm_rows_x3_kernel<2, 32, 2>; break;
+    case 416: kernel = sp_gemm_rows_x3_kernel<4, 16, 1>; break;
+    case 432: kernel = sp_gemm_rows_x3_kernel<4, 32, 1>; break;
     default: return PD3_EUNSUPPORTED;
   }
-#undef PD3_SX
-  return launch_status();
+  const int rc = launch_lds(kernel, grid, 64 * (8 / rb), lds, s, a);
+  return rc ? rc : launch_status();
 }

@@ -417,12 +417,9 @@ extern "C" int pd3_ssd_postprocess(const float* head_map, int64_t batch_stride, 
   ssd_nms_boxes_kernel<<<dim3((cap + 255) / 256, batch), 256, 0, s>>>(w.boxes, sidx, w.counts, (int)a, cap,
                                                                       w.nms_boxes, w.pre, w.pool.xyr);
   nms_enqueue_mask_pooled(w.pre, w.counts, batch, cap, cb, nms_iou_threshold, w.mask, w.pool, s);
-  const size_t lds = nms_sweep_lds(cap);
-  if (lds > 48 * 1024) {
-    e = pd3_max_dynamic_lds(reinterpret_cast<const void*>(nms_sweep_kernel), (int)lds);
-    if (e != hipSuccess) return (int)e;
-  }
-  nms_sweep_kernel<<<batch, kNmsSweepThreads, lds, s>>>(w.mask, w.counts, 0, cap, cb, w.keep, w.nkeep);
+  if (const int rc = launch_lds(nms_sweep_kernel, batch, kNmsSweepThreads, nms_sweep_lds(cap), s, w.mask, w.counts, 0, cap,
+                                cb, w.keep, w.nkeep))
+    return rc;
   ssd_output_kernel<<<batch, 256, 0, s>>>(w.boxes, w.scores, w.labels, sidx, w.counts, w.keep, w.nkeep, (int)a, cap,
                                           nms_pre_max_size, nms_post_max_size, out_boxes, out_scores, out_labels,
                                           out_count);

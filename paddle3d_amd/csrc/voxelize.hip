@@ -276,71 +276,114 @@ static VtWorkspace vt_carve(void* base, int batch, int64_t n, int dim, int max_p
   return w;
 }
 
-// aligned16: the voxels tensor lies at a multiple of 16 bytes, so the float4 row writer runs where P * D % 4 == 0; else the
-// scalar writer runs with four times as many units, and it is THAT count vt_div's x < 2^24 must hold for
-static bool tiled_applicable(const VoxGrid& g, int64_t n, int dim, int max_pts, int max_voxels,
-                             VtPlan& plan, bool aligned16 = true) {
-  plan = vt_plan(g.ncells, n, max_pts);
-  const int64_t row = (int64_t)max_pts * dim;
-  const int64_t rowq = (row % 4 == 0 && aligned16) ? row / 4 : row;
-  return plan.ok && (int64_t)max_voxels * rowq < ((int64_t)1 << 24) - 4096;
+// ---------------------------------------------------------------------------------------------------
+// one call of hard_voxelize: what every form works on (validated and completed by vox_check, below the forms)
+// ---------------------------------------------------------------------------------------------------
+template <typename T>
+struct VoxCall {
+  const T* points;
+  const int32_t* num_points;
+  int batch;
+  int64_t n;
+  int dim;
+  VoxGrid g;
+  int max_pts, max_voxels;
+  T* voxels;  // nullptr: pd3_hard_voxelize_index (no rows are written)
+  int32_t *coords, *num_pts, *num_voxels, *coors4;
+  void* workspace;
+  hipStream_t s;
+};
+
+static VtGrid vt_grid(const VoxGrid& g) {
+  return VtGrid{g.min_x, g.min_y, g.min_z, g.size_x, g.size_y, g.size_z,
+                (float)(1.0 / (double)g.size_x), (float)(1.0 / (double)g.size_y), (float)(1.0 / (double)g.size_z),
+                g.gx, g.gy, g.gz, g.ncells};
 }
 
-static int run_tiled(const float* points, const int32_t* num_points, int batch, int64_t n, int dim,
-                     const VoxGrid& g, int max_pts, int max_voxels, const VtPlan& plan,
-                     float* voxels, int32_t* coords, int32_t* num_pts, int32_t* num_voxels,
-                     int32_t* coors4, void* workspace, hipStream_t s, bool gather) {
-  VtWorkspace w = vt_carve(workspace, batch, n, dim, max_pts, max_voxels, g.ncells, plan);
-  VtGrid vg{g.min_x, g.min_y, g.min_z, g.size_x, g.size_y, g.size_z,
-            (float)(1.0 / (double)g.size_x), (float)(1.0 / (double)g.size_y), (float)(1.0 / (double)g.size_z),
-            g.gx, g.gy, g.gz, g.ncells};
+// Units of one [P, D] row for the gather row writers: float4s where the row is a multiple of four floats and `vec4` (the
+// voxels tensor lies at a multiple of 16 bytes), else floats -- four times as many, and it is THAT count vt_div's
+// x < 2^24 must hold for
+static int64_t vox_rowq(int max_pts, int dim, bool vec4) {
+  const int64_t row = (int64_t)max_pts * dim;
+  return (row % 4 == 0 && vec4) ? row / 4 : row;
+}
+static bool vox_rows_fit(int max_voxels, int64_t rowq) { return (int64_t)max_voxels * rowq < ((int64_t)1 << 24) - 4096; }
+static bool vox_aligned16(const float* voxels) { return reinterpret_cast<uintptr_t>(voxels) % 16 == 0; }
+
+static bool tiled_applicable(const VoxCall<float>& c, VtPlan& plan) {
+  plan = vt_plan(c.g.ncells, c.n, c.max_pts);
+  return plan.ok && vox_rows_fit(c.max_voxels, vox_rowq(c.max_pts, c.dim, vox_aligned16(c.voxels)));
+}
+
+// Launch shape of vt_rows_kernel / vt_rows_gather_kernel<VEC> (VEC = 4 where vec4, else 1)
+struct VtRows {
+  bool vec4;
+  int rowq, units, step_v, step_j;
+  unsigned grid;
+};
+static VtRows vt_rows(const VoxCall<float>& c) {
+  VtRows r;
+  r.rowq = (int)vox_rowq(c.max_pts, c.dim, vox_aligned16(c.voxels));
+  r.vec4 = r.rowq < c.max_pts * c.dim;
+  r.units = (int)ceil_div((int64_t)c.max_voxels * r.rowq, kVtRowsThreads * kVtRowsIlp);
+  r.step_v = kVtRowsThreads / r.rowq;
+  r.step_j = kVtRowsThreads % r.rowq;
+  r.grid = (unsigned)(r.units * c.batch);
+  return r;
+}
+
+// The gather row writer: every row of `voxels` from the points through an index list (any D)
+static void write_rows_gather(const VoxCall<float>& c, const uint32_t* clist, int64_t cap, const uint2* vinfo,
+                              const int* totals) {
+  const VtRows r = vt_rows(c);
+  auto* kernel = r.vec4 ? vt_rows_gather_kernel<4> : vt_rows_gather_kernel<1>;
+  kernel<<<r.grid, kVtRowsThreads, 0, c.s>>>(c.points, c.n, clist, cap, vinfo, totals, c.batch, r.units, c.max_voxels,
+                                             r.rowq, r.step_v, r.step_j, c.dim, c.voxels, c.coords, c.num_pts,
+                                             c.num_voxels, c.coors4);
+}
+
+// The slot-per-lane row writer (D = 4 / 5, voxel * slot below 2^24): one index load, the point's 16 + 4 bytes, the same
+// two streaming stores; a wave writes 64 * D * 4 contiguous bytes
+static bool slot_rows_applicable(int dim, int max_pts, int max_voxels) {
+  return (dim == 4 || dim == 5) && vox_rows_fit(max_voxels, max_pts);
+}
+static void write_rows_slots(const VoxCall<float>& c, const uint32_t* clist, int64_t cap, const uint2* vinfo,
+                             const int* totals) {
+  const int sunits = (int)ceil_div((int64_t)c.max_voxels * c.max_pts, kVwRowsThreads * kVwRowsIlp);
+  auto* kernel = c.dim == 4 ? vw_rows_kernel<4> : vw_rows_kernel<5>;
+  kernel<<<(unsigned)(sunits * c.batch), kVwRowsThreads, 0, c.s>>>(c.points, c.n, clist, cap, vinfo, totals, c.batch, sunits,
+                                                                   c.max_voxels, c.max_pts, c.voxels, c.coords, c.num_pts,
+                                                                   c.num_voxels, c.coors4);
+}
+
+static int run_tiled(const VoxCall<float>& c, const VtPlan& plan, bool gather) {
+  VtWorkspace w = vt_carve(c.workspace, c.batch, c.n, c.dim, c.max_pts, c.max_voxels, c.g.ncells, plan);
+  const VtGrid vg = vt_grid(c.g);
   const size_t lds_a = ((size_t)kVtTile + (size_t)kVtRouteWaves * plan.groups + kVtRouteWaves + 2) * 4;
   const size_t lds_b = vt_group_lds(plan.cpg, plan.tiles);
   // the gather form keeps a list of point indices where the default form keeps the payload itself (same places)
   uint32_t* clist = reinterpret_cast<uint32_t*>(w.compact);
-  const unsigned tile_grid = (unsigned)(plan.tiles * batch);
-  vt_route_kernel<<<tile_grid, kVtRouteThreads, lds_a, s>>>(points, num_points, n, dim, vg, plan.low, plan.gbits,
-                                                            plan.tiles, batch, max_voxels, w.recs, w.dir, w.pos16,
-                                                            w.tilecnt, w.vinfo);
-  vt_group_kernel<<<(unsigned)(plan.groups * batch), kVgThreads, lds_b, s>>>(
-      w.recs, w.dir, plan.low, plan.gbits, plan.tiles, batch, max_pts, w.cposr, w.gstart, w.tilecnt,
+  const unsigned tile_grid = (unsigned)(plan.tiles * c.batch);
+  vt_route_kernel<<<tile_grid, kVtRouteThreads, lds_a, c.s>>>(c.points, c.num_points, c.n, c.dim, vg, plan.low,
+                                                              plan.gbits, plan.tiles, c.batch, c.max_voxels, w.recs,
+                                                              w.dir, w.pos16, w.tilecnt, w.vinfo);
+  vt_group_kernel<<<(unsigned)(plan.groups * c.batch), kVgThreads, lds_b, c.s>>>(
+      w.recs, w.dir, plan.low, plan.gbits, plan.tiles, c.batch, c.max_pts, w.cposr, w.gstart, w.tilecnt,
       gather ? clist : nullptr, w.cap);
   // gather form: only the assign job of the C + D launch runs (the emit job's workgroups are not launched)
-#define PD3_VT_EMIT(D)                                                                                         \
-  vt_assign_emit_kernel<D><<<(gather ? 1 : 2) * tile_grid, kVtRouteThreads, 0, s>>>(                                          \
-      points, n, dim, plan.tiles, batch, w.cposr, w.pos16, w.recs, w.dir, plan.low, plan.gbits, w.tilecnt,      \
-      max_voxels, vg, w.vinfo, w.totals,                                                                       \
-      coords, num_pts, coors4, w.cap, w.compact)
-  switch (dim) {
-    case 4: PD3_VT_EMIT(4); break;
-    case 5: PD3_VT_EMIT(5); break;
-    default: PD3_VT_EMIT(0); break;
-  }
-#undef PD3_VT_EMIT
-  const int64_t row = (int64_t)max_pts * dim;
-  const bool vec4 = (row % 4 == 0) && (reinterpret_cast<uintptr_t>(voxels) % 16 == 0);
-  const int rowq = (int)(vec4 ? row / 4 : row);
-  const int units = (int)ceil_div((int64_t)max_voxels * rowq, kVtRowsThreads * kVtRowsIlp);
-  const int step_v = kVtRowsThreads / rowq, step_j = kVtRowsThreads % rowq;
+  auto* emit = c.dim == 4 ? vt_assign_emit_kernel<4> : (c.dim == 5 ? vt_assign_emit_kernel<5> : vt_assign_emit_kernel<0>);
+  emit<<<(gather ? 1 : 2) * tile_grid, kVtRouteThreads, 0, c.s>>>(
+      c.points, c.n, c.dim, plan.tiles, c.batch, w.cposr, w.pos16, w.recs, w.dir, plan.low, plan.gbits, w.tilecnt,
+      c.max_voxels, vg, w.vinfo, w.totals, c.coords, c.num_pts, c.coors4, w.cap, w.compact);
   if (gather) {
-    if (vec4)
-      vt_rows_gather_kernel<4><<<(unsigned)(units * batch), kVtRowsThreads, 0, s>>>(
-          points, n, clist, w.cap, w.vinfo, w.totals, batch, units, max_voxels, rowq, step_v, step_j, dim, voxels,
-          coords, num_pts, num_voxels, coors4);
-    else
-      vt_rows_gather_kernel<1><<<(unsigned)(units * batch), kVtRowsThreads, 0, s>>>(
-          points, n, clist, w.cap, w.vinfo, w.totals, batch, units, max_voxels, rowq, step_v, step_j, dim, voxels,
-          coords, num_pts, num_voxels, coors4);
+    write_rows_gather(c, clist, w.cap, w.vinfo, w.totals);
     return launch_status();
   }
-  if (vec4)
-    vt_rows_kernel<4><<<(unsigned)(units * batch), kVtRowsThreads, 0, s>>>(
-        w.compact, w.cap, w.vinfo, w.totals, batch, units, max_voxels, rowq, step_v, step_j, dim, voxels, coords,
-        num_pts, num_voxels, coors4);
-  else
-    vt_rows_kernel<1><<<(unsigned)(units * batch), kVtRowsThreads, 0, s>>>(
-        w.compact, w.cap, w.vinfo, w.totals, batch, units, max_voxels, rowq, step_v, step_j, dim, voxels, coords,
-        num_pts, num_voxels, coors4);
+  const VtRows r = vt_rows(c);
+  auto* rows = r.vec4 ? vt_rows_kernel<4> : vt_rows_kernel<1>;
+  rows<<<r.grid, kVtRowsThreads, 0, c.s>>>(w.compact, w.cap, w.vinfo, w.totals, c.batch, r.units, c.max_voxels, r.rowq,
+                                           r.step_v, r.step_j, c.dim, c.voxels, c.coords, c.num_pts, c.num_voxels,
+                                           c.coors4);
   return launch_status();
 }
 
@@ -375,27 +418,27 @@ static VwWorkspace vw_carve(void* base, int batch, int64_t n, int max_voxels, co
   return w;
 }
 
-static bool wave3d_applicable(const VoxGrid& g, int64_t n, int dim, int max_pts, int max_voxels, int batch, int shape,
-                              VwPlan& plan) {
-  plan = v3_plan(g.ncells, n, max_pts, batch, shape);
-  // (the slot-per-lane row writer: D = 4 / 5, voxel * slot below 2^24)
-  return plan.ok && (dim == 4 || dim == 5) && (int64_t)max_voxels * max_pts < ((int64_t)1 << 24) - 4096;
+static bool wave3d_applicable(const VoxCall<float>& c, int shape, VwPlan& plan) {
+  plan = v3_plan(c.g.ncells, c.n, c.max_pts, c.batch, shape);
+  return plan.ok && slot_rows_applicable(c.dim, c.max_pts, c.max_voxels);
 }
 
 constexpr int kVwShapes = 5;
 
-static bool wave_applicable(const VoxGrid& g, int64_t n, int dim, int max_pts, int max_voxels, int batch, int shape,
-                            VwPlan& plan, bool aligned16 = true) {
-  plan = vw_plan(g.ncells, n, max_pts, batch, shape);
-  const int64_t row = (int64_t)max_pts * dim;
+static bool wave_applicable(const VoxCall<float>& c, int shape, VwPlan& plan) {
+  plan = vw_plan(c.g.ncells, c.n, c.max_pts, c.batch, shape);
   // (D = 4 / 5 rows leave through the slot-per-lane writer whatever the alignment: voxel * slot is what counts there)
-  const bool vec4 = aligned16 || dim == 4 || dim == 5;
-  const int64_t rowq = (row % 4 == 0 && vec4) ? row / 4 : row;
-  return plan.ok && (int64_t)max_voxels * rowq < ((int64_t)1 << 24) - 4096;
+  const bool vec4 = vox_aligned16(c.voxels) || c.dim == 4 || c.dim == 5;
+  return plan.ok && vox_rows_fit(c.max_voxels, vox_rowq(c.max_pts, c.dim, vec4));
 }
 
-// variant bit 0: heavy waves of the group kernel raise their issue priority; bit 1 (run_wave_split): two half batches
-// on two streams
+// variants of the wave form (bits)
+enum : int {
+  kVwPriority = 1,    // heavy waves of the group kernel raise their issue priority
+  kVwTwoStreams = 2,  // run_wave_split: two half batches on two streams
+  kVwCarry = 4,       // measurement: the points' payload carried through the route kernel's LDS slice
+};
+
 // index_span / index_list (pd3_hard_voxelize_index): the per-voxel (start, count) words and the index list are left in
 // the CALLER's arrays instead of the workspace, and the row writer does not run (voxels == nullptr): what remains of it
 // is vw_finish_index_kernel (num_voxels, the padding rows of coords / counts / coors_batched).
@@ -416,96 +459,59 @@ __global__ __launch_bounds__(256) void vw_finish_index_kernel(const int* __restr
   }
 }
 
-static int run_wave(const float* points, const int32_t* num_points, int batch, int64_t n, int dim, const VoxGrid& g,
-                    int max_pts, int max_voxels, const VwPlan& plan, float* voxels, int32_t* coords,
-                    int32_t* num_pts, int32_t* num_voxels, int32_t* coors4, void* workspace, hipStream_t s,
-                    int variant = 0, int frame0 = 0, bool three_d = false, int32_t* index_span = nullptr,
-                    int32_t* index_list = nullptr) {
-  VwWorkspace w = vw_carve(workspace, batch, n, max_voxels, plan, three_d);
+static int run_wave(const VoxCall<float>& c, const VwPlan& plan, int variant = 0, int frame0 = 0, bool three_d = false,
+                    int32_t* index_span = nullptr, int32_t* index_list = nullptr) {
+  VwWorkspace w = vw_carve(c.workspace, c.batch, c.n, c.max_voxels, plan, three_d);
   if (index_span) {
     w.vinfo = reinterpret_cast<uint2*>(index_span);
     w.clist = reinterpret_cast<uint32_t*>(index_list);
   }
-  VtGrid vg{g.min_x, g.min_y, g.min_z, g.size_x, g.size_y, g.size_z,
-            (float)(1.0 / (double)g.size_x), (float)(1.0 / (double)g.size_y), (float)(1.0 / (double)g.size_z),
-            g.gx, g.gy, g.gz, g.ncells};
-  if (g.gz == 1 && !vt_single_cell_bounds(g.size_z, vg.z1_lo, vg.z1_hi)) vg.z1_lo = 0.f, vg.z1_hi = -1.f;
+  VtGrid vg = vt_grid(c.g);
+  if (c.g.gz == 1 && !vt_single_cell_bounds(c.g.size_z, vg.z1_lo, vg.z1_hi)) vg.z1_lo = 0.f, vg.z1_hi = -1.f;
   const int waves = plan.threads / kWave;
-  const bool pay = (variant & 4) != 0 && voxels != nullptr;  // path 17: payload carried through the route kernel
+  const bool pay = (variant & kVwCarry) != 0 && c.voxels != nullptr;
+  // up to ~104 KB of dynamic LDS (1024 x 10 tile)
   const size_t lds_a = ((size_t)plan.tile + (size_t)waves * plan.groups + waves + 2) * 4 +
-                       (pay ? (size_t)plan.tile * dim * 4 : 0);
-  const unsigned tile_grid = (unsigned)(plan.tiles * batch);
-  // up to ~104 KB of dynamic LDS (1024 x 10 tile): above the 48 KB a kernel may use without asking, so the cap is
-  // raised per instantiation like every other large-LDS kernel of the library (a host-side table write per launch)
-#define PD3_VW_ROUTE(T, R)                                                                                         \
-  do {                                                                                                             \
-    const hipError_t e_ = pd3_max_dynamic_lds(reinterpret_cast<const void*>(vw_route_kernel<T, R>), (int)lds_a);             \
-    if (e_ != hipSuccess) return (int)e_;                                                                          \
-    vw_route_kernel<T, R><<<tile_grid, T, lds_a, s>>>(points, num_points, n, dim, vg, plan.low, plan.gbits,        \
-                                                      plan.tiles, batch, max_voxels, w.recs, w.dir, w.vinfo,       \
-                                                      three_d ? 1 : 0);                                            \
-  } while (0)
-  if (pay) {
-    // (measurement form) the carried payload goes to the head of the `voxels` buffer, which the row writer overwrites
-    if (plan.threads != 512 || plan.rounds != 8 || lds_a > 160 * 1024 ||
-        (int64_t)batch * plan.tiles * plan.tile * dim > (int64_t)batch * max_voxels * max_pts * dim)
-      return PD3_EUNSUPPORTED;
-    const hipError_t e_ = pd3_max_dynamic_lds(reinterpret_cast<const void*>(vw_route_kernel<512, 8, true>), (int)lds_a);
-    if (e_ != hipSuccess) return (int)e_;
-    vw_route_kernel<512, 8, true><<<tile_grid, 512, lds_a, s>>>(points, num_points, n, dim, vg, plan.low, plan.gbits,
-                                                                plan.tiles, batch, max_voxels, w.recs, w.dir, w.vinfo,
-                                                                three_d ? 1 : 0, voxels);
-  } else
-  if (plan.threads == 512 && plan.rounds == 8) PD3_VW_ROUTE(512, 8);
-  else if (plan.threads == 1024 && plan.rounds == 8) PD3_VW_ROUTE(1024, 8);
-  else if (plan.threads == 1024 && plan.rounds == 10) PD3_VW_ROUTE(1024, 10);
-  else if (plan.threads == 512 && plan.rounds == 10) PD3_VW_ROUTE(512, 10);
-  else if (plan.threads == 1024 && plan.rounds == 5) PD3_VW_ROUTE(1024, 5);
+                       (pay ? (size_t)plan.tile * c.dim * 4 : 0);
+  const unsigned tile_grid = (unsigned)(plan.tiles * c.batch);
+  // (measurement form) the carried payload goes to the head of the `voxels` buffer, which the row writer overwrites
+  if (pay && (plan.threads != 512 || plan.rounds != 8 || lds_a > 160 * 1024 ||
+              (int64_t)c.batch * plan.tiles * plan.tile * c.dim > (int64_t)c.batch * c.max_voxels * c.max_pts * c.dim))
+    return PD3_EUNSUPPORTED;
+  auto route = [&](auto kernel) {
+    return launch_lds(kernel, tile_grid, plan.threads, lds_a, c.s, c.points, c.num_points, c.n, c.dim, vg, plan.low,
+                      plan.gbits, plan.tiles, c.batch, c.max_voxels, w.recs, w.dir, w.vinfo, three_d ? 1 : 0,
+                      pay ? c.voxels : nullptr);
+  };
+  int rc;
+  if (pay) rc = route(vw_route_kernel<512, 8, true>);
+  else if (plan.threads == 512 && plan.rounds == 8) rc = route(vw_route_kernel<512, 8>);
+  else if (plan.threads == 1024 && plan.rounds == 8) rc = route(vw_route_kernel<1024, 8>);
+  else if (plan.threads == 1024 && plan.rounds == 10) rc = route(vw_route_kernel<1024, 10>);
+  else if (plan.threads == 512 && plan.rounds == 10) rc = route(vw_route_kernel<512, 10>);
+  else if (plan.threads == 1024 && plan.rounds == 5) rc = route(vw_route_kernel<1024, 5>);
   else return PD3_EINVAL;
-#undef PD3_VW_ROUTE
+  if (rc != 0) return rc;
   const int tp = vw_pow2_above(plan.tiles);
   if (three_d)
-    v3_group_kernel<<<(unsigned)(plan.groups * batch), kWave, v3_group_lds(plan.tiles), s>>>(
-        w.recs, w.dir, plan.gbits, plan.tiles, plan.tile, tp, batch, max_pts, w.clist, w.cap, w.flist, w.fcnt,
+    v3_group_kernel<<<(unsigned)(plan.groups * c.batch), kWave, v3_group_lds(plan.tiles), c.s>>>(
+        w.recs, w.dir, plan.gbits, plan.tiles, plan.tile, tp, c.batch, c.max_pts, w.clist, w.cap, w.flist, w.fcnt,
         w.gregion, w.aux);
   else
-    vw_group_kernel<<<(unsigned)(plan.groups * batch), kWave, vw_group_lds(plan.cpg, plan.tiles), s>>>(
-        w.recs, w.dir, plan.low, plan.gbits, plan.tiles, plan.tile, tp, batch, max_pts, w.clist, w.cap, w.flist,
-        w.fcnt, (variant & 1) ? (uint32_t)std::max<int64_t>(n / plan.groups, 1) : 0u);
+    vw_group_kernel<<<(unsigned)(plan.groups * c.batch), kWave, vw_group_lds(plan.cpg, plan.tiles), c.s>>>(
+        w.recs, w.dir, plan.low, plan.gbits, plan.tiles, plan.tile, tp, c.batch, c.max_pts, w.clist, w.cap, w.flist,
+        w.fcnt, (variant & kVwPriority) ? (uint32_t)std::max<int64_t>(c.n / plan.groups, 1) : 0u);
   const size_t lds_c = (size_t)2 * (((size_t)plan.tile + 31) / 32) * 4 + (size_t)kVwAssignCap * 8;
-  vw_assign_kernel<<<(unsigned)(plan.tiles * batch), kVwAssignThreads, lds_c, s>>>(
-      w.flist, w.fcnt, plan.low, plan.gbits, plan.tiles, plan.tile, tp, batch, max_voxels, vg, w.vinfo, w.totals, coords,
-      num_pts, coors4, frame0, three_d ? w.gregion : nullptr, w.cap);
-  if (index_span) {
-    vw_finish_index_kernel<<<(unsigned)ceil_div((int64_t)batch * max_voxels, 256), 256, 0, s>>>(
-        w.totals, batch, max_voxels, coords, num_pts, num_voxels, coors4);
-    return launch_status();
-  }
-  const int64_t row = (int64_t)max_pts * dim;
-  const bool vec4 = (row % 4 == 0) && (reinterpret_cast<uintptr_t>(voxels) % 16 == 0);
-  const int rowq = (int)(vec4 ? row / 4 : row);
-  const int units = (int)ceil_div((int64_t)max_voxels * rowq, kVtRowsThreads * kVtRowsIlp);
-  const int step_v = kVtRowsThreads / rowq, step_j = kVtRowsThreads % rowq;
-  if (dim == 4 || dim == 5) {
-    const int64_t slots = (int64_t)max_voxels * max_pts;
-    const int sunits = (int)ceil_div(slots, kVwRowsThreads * kVwRowsIlp);
-#define PD3_VW_ROWS(D)                                                                                            \
-  vw_rows_kernel<D><<<(unsigned)(sunits * batch), kVwRowsThreads, 0, s>>>(                                   \
-      points, n, w.clist, w.cap, w.vinfo, w.totals, batch, sunits, max_voxels, max_pts, voxels, coords, num_pts,   \
-      num_voxels, coors4)
-    if (dim == 4) PD3_VW_ROWS(4);
-    else PD3_VW_ROWS(5);
-#undef PD3_VW_ROWS
-    return launch_status();
-  }
-  if (vec4)
-    vt_rows_gather_kernel<4><<<(unsigned)(units * batch), kVtRowsThreads, 0, s>>>(
-        points, n, w.clist, w.cap, w.vinfo, w.totals, batch, units, max_voxels, rowq, step_v, step_j, dim, voxels,
-        coords, num_pts, num_voxels, coors4);
+  vw_assign_kernel<<<(unsigned)(plan.tiles * c.batch), kVwAssignThreads, lds_c, c.s>>>(
+      w.flist, w.fcnt, plan.low, plan.gbits, plan.tiles, plan.tile, tp, c.batch, c.max_voxels, vg, w.vinfo, w.totals,
+      c.coords, c.num_pts, c.coors4, frame0, three_d ? w.gregion : nullptr, w.cap);
+  if (index_span)
+    vw_finish_index_kernel<<<(unsigned)ceil_div((int64_t)c.batch * c.max_voxels, 256), 256, 0, c.s>>>(
+        w.totals, c.batch, c.max_voxels, c.coords, c.num_pts, c.num_voxels, c.coors4);
+  else if (c.dim == 4 || c.dim == 5)
+    write_rows_slots(c, w.clist, w.cap, w.vinfo, w.totals);
   else
-    vt_rows_gather_kernel<1><<<(unsigned)(units * batch), kVtRowsThreads, 0, s>>>(
-        points, n, w.clist, w.cap, w.vinfo, w.totals, batch, units, max_voxels, rowq, step_v, step_j, dim, voxels,
-        coords, num_pts, num_voxels, coors4);
+    write_rows_gather(c, w.clist, w.cap, w.vinfo, w.totals);
   return launch_status();
 }
 
@@ -514,18 +520,13 @@ static int run_wave(const float* points, const int32_t* num_points, int batch, i
 // idle tail at every boundary; two independent chains let the hardware run one half's latency-bound kernels beside
 // the other half's streaming ones.  Fork / join by events on the caller's stream, so the op stays one unit of work
 // on that stream (and stays capturable).  Same bytes out: every frame is processed by the same kernels.
-static int run_wave_split(const float* points, const int32_t* num_points, int batch, int64_t n, int dim,
-                          const VoxGrid& g, int max_pts, int max_voxels, const VwPlan& plan, float* voxels,
-                          int32_t* coords, int32_t* num_pts, int32_t* num_voxels, int32_t* coors4, void* workspace,
-                          hipStream_t s, int variant) {
+static int run_wave_split(const VoxCall<float>& c, const VwPlan& plan, int variant) {
   constexpr int kMaxDev = 16;
   static hipStream_t side[kMaxDev] = {};
   static hipEvent_t fork_ev[kMaxDev] = {}, join_ev[kMaxDev] = {};
   static std::mutex mu;
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev || batch < 2)
-    return run_wave(points, num_points, batch, n, dim, g, max_pts, max_voxels, plan, voxels, coords, num_pts,
-                    num_voxels, coors4, workspace, s, variant);
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev || c.batch < 2) return run_wave(c, plan, variant);
   // One side stream and one fork / join event pair per device, shared by every caller: the lock is held from the fork
   // to the join so that two host threads on different streams of one device cannot interleave their records and waits
   // (this is a measurement form; the library's own choice never takes it).
@@ -545,77 +546,124 @@ static int run_wave_split(const float* points, const int32_t* num_points, int ba
     join_ev[dev] = ej;
     side[dev] = st;
   }
-  const int b0 = batch / 2, b1 = batch - b0;
-  const size_t half_bytes = align_up(vw_carve(nullptr, b0, n, max_voxels, plan).bytes, 256);
-  const int64_t vrow = (int64_t)max_voxels * max_pts * dim;
-  hipError_t e = hipEventRecord(fork_ev[dev], s);
+  // frames [0, b0) stay on the caller's stream; frames [b0, batch) go to the side stream with a workspace region of
+  // their own behind the first half's
+  const int b0 = c.batch / 2;
+  VoxCall<float> lo = c, hi = c;
+  lo.batch = b0;
+  hi.batch = c.batch - b0;
+  hi.points += (int64_t)b0 * c.n * c.dim;
+  if (hi.num_points) hi.num_points += b0;
+  hi.voxels += (int64_t)b0 * c.max_voxels * c.max_pts * c.dim;
+  hi.coords += (int64_t)b0 * c.max_voxels * 3;
+  hi.num_pts += (int64_t)b0 * c.max_voxels;
+  hi.num_voxels += b0;
+  if (hi.coors4) hi.coors4 += (int64_t)b0 * c.max_voxels * 4;
+  hi.workspace = static_cast<char*>(c.workspace) + align_up(vw_carve(nullptr, b0, c.n, c.max_voxels, plan).bytes, 256);
+  hi.s = side[dev];
+  hipError_t e = hipEventRecord(fork_ev[dev], c.s);
   if (e == hipSuccess) e = hipStreamWaitEvent(side[dev], fork_ev[dev], 0);
   if (e != hipSuccess) return (int)e;
-  int rc = run_wave(points, num_points, b0, n, dim, g, max_pts, max_voxels, plan, voxels, coords, num_pts, num_voxels,
-                    coors4, workspace, s, variant);
+  int rc = run_wave(lo, plan, variant);
   if (rc != 0) return rc;
-  rc = run_wave(points + (int64_t)b0 * n * dim, num_points ? num_points + b0 : nullptr, b1, n, dim, g, max_pts,
-                max_voxels, plan, voxels + (int64_t)b0 * vrow, coords + (int64_t)b0 * max_voxels * 3,
-                num_pts + (int64_t)b0 * max_voxels, num_voxels + b0,
-                coors4 ? coors4 + (int64_t)b0 * max_voxels * 4 : nullptr, static_cast<char*>(workspace) + half_bytes,
-                side[dev], variant, b0);
+  rc = run_wave(hi, plan, variant, b0);
   if (rc != 0) return rc;
   e = hipEventRecord(join_ev[dev], side[dev]);
-  if (e == hipSuccess) e = hipStreamWaitEvent(s, join_ev[dev], 0);
+  if (e == hipSuccess) e = hipStreamWaitEvent(c.s, join_ev[dev], 0);
   return e == hipSuccess ? 0 : (int)e;
 }
 
 // generic path: stable radix sort of (cell, index), segment heads, flag scan in point order, voxel-parallel gather
 template <typename T>
-static int run_sort_path(const T* points, const int32_t* num_points, int batch, int64_t n, int num_point_dim,
-                         const VoxGrid& g, int max_num_points_in_voxel, int max_voxels, T* voxels, int32_t* coords,
-                         int32_t* num_points_per_voxel, int32_t* num_voxels, int32_t* coors_batched, void* workspace,
-                         hipStream_t s) {
-  const int64_t max_points = n;
-  const RadixPlan plan = radix_plan(g.ncells, max_points);
-  VoxWorkspace w = carve(workspace, batch, max_points, max_voxels, plan);
+static int run_sort_path(const VoxCall<T>& c) {
+  const int64_t n = c.n;
+  const RadixPlan plan = radix_plan(c.g.ncells, n);
+  VoxWorkspace w = carve(c.workspace, c.batch, n, c.max_voxels, plan);
+  hipStream_t s = c.s;
 
-  dim3 pgrid((unsigned)ceil_div(n, 256), batch);
-  cell_key_kernel<T><<<pgrid, 256, 0, s>>>(points, num_points, n, num_point_dim, g, w.keys_a);
-  const int where = enqueue_radix_sort(w.keys_a, w.vals_a, w.keys_b, w.vals_b, n, n, batch, plan,
+  dim3 pgrid((unsigned)ceil_div(n, 256), c.batch);
+  cell_key_kernel<T><<<pgrid, 256, 0, s>>>(c.points, c.num_points, n, c.dim, c.g, w.keys_a);
+  const int where = enqueue_radix_sort(w.keys_a, w.vals_a, w.keys_b, w.vals_b, n, n, c.batch, plan,
                                        /*identity_vals=*/true, w.hist, w.partial, s);
   const uint32_t* skey = where ? w.keys_b : w.keys_a;
   const uint32_t* sidx = where ? w.vals_b : w.vals_a;
-  seg_head_kernel<<<pgrid, 256, 0, s>>>(skey, sidx, n, g.ncells, w.mark);
-  EpiVoxelStart epi{w.mark, w.vox_start, n, max_voxels};
-  enqueue_exclusive_scan(w.mark, n, n, batch, w.partial, w.totals, (int*)nullptr, LoadNonNegative{},
+  seg_head_kernel<<<pgrid, 256, 0, s>>>(skey, sidx, n, c.g.ncells, w.mark);
+  EpiVoxelStart epi{w.mark, w.vox_start, n, c.max_voxels};
+  enqueue_exclusive_scan(w.mark, n, n, c.batch, w.partial, w.totals, (int*)nullptr, LoadNonNegative{},
                          epi, s);
-  dim3 mgrid((unsigned)ceil_div(max_voxels, 256), batch);
-  // fp32 points of 4 / 5 floats: the fixed-shape rows are written by the wave form's slot-per-lane row writer (one
-  // index load, the point's 16 + 4 bytes, the same two streaming stores; a wave writes 64 * D * 4 contiguous bytes),
-  // with the sorted index list as its `clist`.  The float-per-thread gather it replaces here spent 205 us per 8
-  // frames of config 4 (1.25 TB/s) on three divisions and three dependent loads per output float.
-  const int64_t slots = (int64_t)max_voxels * max_num_points_in_voxel;
+  dim3 mgrid((unsigned)ceil_div(c.max_voxels, 256), c.batch);
+  // fp32 points of 4 / 5 floats: the fixed-shape rows are written by the wave form's slot-per-lane row writer, with the
+  // sorted index list as its `clist`.  The float-per-thread gather it replaces here spent 205 us per 8 frames of
+  // config 4 (1.25 TB/s) on three divisions and three dependent loads per output float.
   if constexpr (std::is_same<T, float>::value) {
-    if ((num_point_dim == 4 || num_point_dim == 5) && slots < ((int64_t)1 << 24) - 4096) {
-      voxel_meta_kernel<<<mgrid, 256, 0, s>>>(skey, w.vox_start, w.totals, n, max_num_points_in_voxel, max_voxels, g,
-                                              coords, num_points_per_voxel, num_voxels, coors_batched, w.vinfo);
-      const int sunits = (int)ceil_div(slots, kVwRowsThreads * kVwRowsIlp);
-      if (num_point_dim == 4)
-        vw_rows_kernel<4><<<(unsigned)(sunits * batch), kVwRowsThreads, 0, s>>>(
-            points, n, sidx, n, w.vinfo, w.totals, batch, sunits, max_voxels, max_num_points_in_voxel, voxels, coords,
-            num_points_per_voxel, num_voxels, coors_batched);
-      else
-        vw_rows_kernel<5><<<(unsigned)(sunits * batch), kVwRowsThreads, 0, s>>>(
-            points, n, sidx, n, w.vinfo, w.totals, batch, sunits, max_voxels, max_num_points_in_voxel, voxels, coords,
-            num_points_per_voxel, num_voxels, coors_batched);
+    if (slot_rows_applicable(c.dim, c.max_pts, c.max_voxels)) {
+      voxel_meta_kernel<<<mgrid, 256, 0, s>>>(skey, w.vox_start, w.totals, n, c.max_pts, c.max_voxels, c.g, c.coords,
+                                              c.num_pts, c.num_voxels, c.coors4, w.vinfo);
+      write_rows_slots(c, sidx, n, w.vinfo, w.totals);
       return launch_status();
     }
   }
-  const int64_t per_frame = slots * num_point_dim;
-  dim3 ggrid((unsigned)ceil_div(per_frame, 256), batch);
-  gather_voxels_kernel<T><<<ggrid, 256, 0, s>>>(points, skey, sidx, w.vox_start, w.totals, n,
-                                                num_point_dim, max_num_points_in_voxel, max_voxels,
-                                                voxels);
-  voxel_meta_kernel<<<mgrid, 256, 0, s>>>(skey, w.vox_start, w.totals, n, max_num_points_in_voxel,
-                                          max_voxels, g, coords, num_points_per_voxel, num_voxels, coors_batched,
-                                          nullptr);
+  const int64_t per_frame = (int64_t)c.max_voxels * c.max_pts * c.dim;
+  dim3 ggrid((unsigned)ceil_div(per_frame, 256), c.batch);
+  gather_voxels_kernel<T><<<ggrid, 256, 0, s>>>(c.points, skey, sidx, w.vox_start, w.totals, n, c.dim, c.max_pts,
+                                                c.max_voxels, c.voxels);
+  voxel_meta_kernel<<<mgrid, 256, 0, s>>>(skey, w.vox_start, w.totals, n, c.max_pts, c.max_voxels, c.g, c.coords,
+                                          c.num_pts, c.num_voxels, c.coors4, nullptr);
   return launch_status();
+}
+
+// The path selector of pd3_hard_voxelize_path, decoded: the form, the route-tile shape forced on it (-1: chosen from
+// the sizes) and the variant bits of the wave form.
+enum VoxForm {
+  kFormAuto,         // the library's choice: wave form (2-D, else 3-D), else the tiled gather form, else the sort path
+  kFormSort,         // stable radix sort of (cell, index), segment heads, flag scan in point order, voxel-parallel gather
+  kFormTiled,        // voxelize_tiled.hpp, the payload kept in the workspace
+  kFormTiledGather,  // the same with a list of point indices instead
+  kFormWave,         // voxelize_wave.hpp
+  kFormWave3d,       // voxelize_wave3d.hpp: the wave form for 3-D grids
+};
+struct VoxPath {
+  VoxForm form;
+  int shape, variant;
+};
+constexpr VoxPath kVoxPaths[] = {
+    // 0: (heavy group waves at raised issue priority: 112.8-116.2 against 113.1-122.1 us per 16 frames in four A/B pairs
+    //  on two boxes, profiles/r04_vox_paths.txt; path 5 is the same without it)
+    {kFormAuto, -1, kVwPriority},
+    {kFormSort, -1, 0},         // 1
+    {kFormTiled, -1, 0},        // 2
+    {kFormTiledGather, -1, 0},  // 3
+    {kFormTiledGather, -1, 0},  // 4 (no form of its own)
+    {kFormWave, -1, 0},         // 5
+    {kFormWave, 0, 0},          // 6 .. 5 + kVwShapes: the route-tile shape forced (measurement)
+    {kFormWave, 1, 0},
+    {kFormWave, 2, 0},
+    {kFormWave, 3, 0},
+    {kFormWave, 4, 0},
+    {kFormWave, -1, kVwPriority},  // 11 .. 13: measurement variants of the wave form
+    {kFormWave, -1, kVwTwoStreams},
+    {kFormWave, -1, kVwPriority | kVwTwoStreams},
+    {kFormWave3d, -1, 0},  // 14; 15 / 16: its route tile forced to 8192 / 10240 points
+    {kFormWave3d, 1, 0},
+    {kFormWave3d, 2, 0},
+    {kFormWave, 0, kVwPriority | kVwCarry},  // 17 measurement: path 6 (4096-point route tiles) + the carried payload
+};
+constexpr int kVoxPathCount = (int)(sizeof(kVoxPaths) / sizeof(kVoxPaths[0]));
+static_assert(kVoxPathCount == 18 && kVwShapes == 5, "the selector values 0 .. 17 are part of the ABI");
+
+// What the three entry points check before anything runs, in this order (it decides which status wins when two things are
+// wrong): null pointers, numeric ranges, the grid and the path selector, the workspace size.  Fills c.g.
+// rows_out: the entry's own row output is there (voxels; or the span and list arrays of pd3_hard_voxelize_index).
+template <typename T>
+static int vox_check(VoxCall<T>& c, bool rows_out, const float* voxel_size, const float* range, int path,
+                     size_t workspace_bytes) {
+  if (!c.points || !rows_out || !c.coords || !c.num_pts || !c.num_voxels || !c.workspace) return PD3_EINVAL;
+  if (c.batch <= 0 || c.n <= 0 || c.n >= ((int64_t)1 << 31) || c.dim < 3 || c.max_pts <= 0 || c.max_voxels <= 0)
+    return PD3_EINVAL;
+  if (!make_grid(voxel_size, range, c.g) || path < 0 || path >= kVoxPathCount) return PD3_EINVAL;
+  if (workspace_bytes < pd3_hard_voxelize_workspace(c.batch, c.n, c.dim, voxel_size, range, c.max_pts, c.max_voxels))
+    return PD3_EWORKSPACE;
+  return 0;
 }
 
 }  // namespace pd3
@@ -626,18 +674,23 @@ extern "C" size_t pd3_hard_voxelize_workspace(int batch, int64_t max_points, int
                                               const float* voxel_size,
                                               const float* point_cloud_range,
                                               int max_num_points_in_voxel, int max_voxels) {
-  VoxGrid g;
-  if (batch <= 0 || max_points <= 0 || max_voxels <= 0 || !make_grid(voxel_size, point_cloud_range, g))
+  VoxCall<float> c{};  // the sizes only (no voxels tensor: the aligned row writers)
+  c.batch = batch;
+  c.n = max_points;
+  c.dim = num_point_dim;
+  c.max_pts = max_num_points_in_voxel;
+  c.max_voxels = max_voxels;
+  if (batch <= 0 || max_points <= 0 || max_voxels <= 0 || !make_grid(voxel_size, point_cloud_range, c.g))
     return 0;
-  const RadixPlan plan = radix_plan(g.ncells, max_points);
+  const RadixPlan plan = radix_plan(c.g.ncells, max_points);
   size_t bytes = carve(nullptr, batch, max_points, max_voxels, plan).bytes;
   VtPlan vp;
-  if (tiled_applicable(g, max_points, num_point_dim, max_num_points_in_voxel, max_voxels, vp))
+  if (tiled_applicable(c, vp))
     bytes = std::max(bytes, vt_carve(nullptr, batch, max_points, num_point_dim, max_num_points_in_voxel, max_voxels,
-                                     g.ncells, vp).bytes);
+                                     c.g.ncells, vp).bytes);
   for (int shape = -1; shape < kVwShapes; ++shape) {
     VwPlan wp;
-    if (wave_applicable(g, max_points, num_point_dim, max_num_points_in_voxel, max_voxels, batch, shape, wp)) {
+    if (wave_applicable(c, shape, wp)) {
       bytes = std::max(bytes, vw_carve(nullptr, batch, max_points, max_voxels, wp).bytes);
       if (batch >= 2)  // the two-stream form carves one region per half batch
         bytes = std::max(bytes, align_up(vw_carve(nullptr, batch / 2, max_points, max_voxels, wp).bytes, 256) +
@@ -646,7 +699,7 @@ extern "C" size_t pd3_hard_voxelize_workspace(int batch, int64_t max_points, int
   }
   for (int shape = -1; shape < 3; ++shape) {
     VwPlan wp;
-    if (wave3d_applicable(g, max_points, num_point_dim, max_num_points_in_voxel, max_voxels, batch, shape, wp))
+    if (wave3d_applicable(c, shape, wp))
       bytes = std::max(bytes, vw_carve(nullptr, batch, max_points, max_voxels, wp, true).bytes);
   }
   return bytes;
@@ -659,77 +712,34 @@ extern "C" int pd3_hard_voxelize_path(const float* points, const int32_t* num_po
                                       int32_t* num_points_per_voxel, int32_t* num_voxels,
                                       int32_t* coors_batched, void* workspace, size_t workspace_bytes,
                                       void* stream, int path) {
-  VoxGrid g;
-  if (!points || !voxels || !coords || !num_points_per_voxel || !num_voxels || !workspace)
-    return PD3_EINVAL;
-  if (batch <= 0 || max_points <= 0 || max_points >= ((int64_t)1 << 31) || num_point_dim < 3 ||
-      max_num_points_in_voxel <= 0 || max_voxels <= 0)
-    return PD3_EINVAL;
-  // paths: 0 the library's choice; 1 sort; 2 / 3 tiled forms; 5 wave form; 6 .. 5 + kVwShapes wave form with a forced
-  // route-tile shape; 11 wave form + wave priorities; 12 wave form as two half batches on two streams; 13 both;
-  // 14 the wave form for 3-D grids (voxelize_wave3d.hpp; 15 / 16: its route tile forced to 8192 / 10240 points);
-  // 17 measurement: path 6 (4096-point route tiles) + the points' payload carried through the route kernel's LDS slice
-  if (!make_grid(voxel_size, point_cloud_range, g) || path < 0 || path > 17) return PD3_EINVAL;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int64_t n = max_points;
-  const bool al16 = reinterpret_cast<uintptr_t>(voxels) % 16 == 0;  // which row writer runs (see tiled_applicable)
-  if (workspace_bytes < pd3_hard_voxelize_workspace(batch, max_points, num_point_dim, voxel_size,
-                                                    point_cloud_range, max_num_points_in_voxel,
-                                                    max_voxels))
-    return PD3_EWORKSPACE;
-  if (path == 17) {  // measurement: the wave form (4096-point route tiles) with the payload carried through the route
-    VwPlan wp;
-    if (!wave_applicable(g, n, num_point_dim, max_num_points_in_voxel, max_voxels, batch, 0, wp, al16)) return PD3_EUNSUPPORTED;
-    return run_wave(points, num_points, batch, n, num_point_dim, g, max_num_points_in_voxel, max_voxels, wp, voxels,
-                    coords, num_points_per_voxel, num_voxels, coors_batched, workspace, s, 1 | 4);
+  VoxCall<float> c{points, num_points, batch, max_points, num_point_dim, {}, max_num_points_in_voxel, max_voxels,
+                   voxels, coords, num_points_per_voxel, num_voxels, coors_batched, workspace,
+                   static_cast<hipStream_t>(stream)};
+  if (const int rc = vox_check(c, voxels != nullptr, voxel_size, point_cloud_range, path, workspace_bytes))
+    return rc;
+  const VoxPath p = kVoxPaths[path];
+  VwPlan wp;
+  VtPlan vp;
+  switch (p.form) {
+    case kFormWave:
+      if (!wave_applicable(c, p.shape, wp)) return PD3_EUNSUPPORTED;
+      return (p.variant & kVwTwoStreams) ? run_wave_split(c, wp, p.variant) : run_wave(c, wp, p.variant);
+    case kFormWave3d:
+      if (!wave3d_applicable(c, p.shape, wp)) return PD3_EUNSUPPORTED;
+      return run_wave(c, wp, 0, 0, true);
+    case kFormTiled:
+    case kFormTiledGather:
+      if (!tiled_applicable(c, vp)) return PD3_EUNSUPPORTED;
+      return run_tiled(c, vp, p.form == kFormTiledGather);
+    case kFormSort:
+      return run_sort_path(c);
+    case kFormAuto:
+      break;
   }
-  if (path >= 14) {
-    VwPlan wp;
-    if (!wave3d_applicable(g, n, num_point_dim, max_num_points_in_voxel, max_voxels, batch, path == 14 ? -1 : path - 14, wp))
-      return PD3_EUNSUPPORTED;
-    return run_wave(points, num_points, batch, n, num_point_dim, g, max_num_points_in_voxel, max_voxels, wp, voxels,
-                    coords, num_points_per_voxel, num_voxels, coors_batched, workspace, s, 0, 0, true);
-  }
-  if (path >= 11) {  // measurement variants of the wave form
-    VwPlan wp;
-    if (!wave_applicable(g, n, num_point_dim, max_num_points_in_voxel, max_voxels, batch, -1, wp, al16))
-      return PD3_EUNSUPPORTED;
-    const int variant = path == 11 ? 1 : (path == 12 ? 2 : 3);
-    if (variant & 2)
-      return run_wave_split(points, num_points, batch, n, num_point_dim, g, max_num_points_in_voxel, max_voxels, wp,
-                            voxels, coords, num_points_per_voxel, num_voxels, coors_batched, workspace, s, variant);
-    return run_wave(points, num_points, batch, n, num_point_dim, g, max_num_points_in_voxel, max_voxels, wp, voxels,
-                    coords, num_points_per_voxel, num_voxels, coors_batched, workspace, s, variant);
-  }
-  if (path >= 5) {  // wave form: 5 = shape chosen from the sizes, 6 .. = route-kernel shape forced (measurement)
-    VwPlan wp;
-    if (!wave_applicable(g, n, num_point_dim, max_num_points_in_voxel, max_voxels, batch, path - 6, wp, al16))
-      return PD3_EUNSUPPORTED;
-    return run_wave(points, num_points, batch, n, num_point_dim, g, max_num_points_in_voxel, max_voxels, wp, voxels,
-                    coords, num_points_per_voxel, num_voxels, coors_batched, workspace, s);
-  }
-  if (path == 0) {  // the library's choice: wave form (2-D, else 3-D), else the tiled gather form, else the sort path
-    VwPlan wp;
-    // (heavy group waves at raised issue priority: 112.8-116.2 against 113.1-122.1 us per 16 frames in four A/B pairs
-    //  on two boxes, profiles/r04_vox_paths.txt; path 5 is the same without it)
-    if (wave_applicable(g, n, num_point_dim, max_num_points_in_voxel, max_voxels, batch, -1, wp, al16))
-      return run_wave(points, num_points, batch, n, num_point_dim, g, max_num_points_in_voxel, max_voxels, wp, voxels,
-                      coords, num_points_per_voxel, num_voxels, coors_batched, workspace, s, 1);
-    if (wave3d_applicable(g, n, num_point_dim, max_num_points_in_voxel, max_voxels, batch, -1, wp))
-      return run_wave(points, num_points, batch, n, num_point_dim, g, max_num_points_in_voxel, max_voxels, wp, voxels,
-                      coords, num_points_per_voxel, num_voxels, coors_batched, workspace, s, 0, 0, true);
-  }
-  {
-    VtPlan vp;
-    const bool can = tiled_applicable(g, n, num_point_dim, max_num_points_in_voxel, max_voxels, vp, al16);
-    if (path >= 2 && !can) return PD3_EUNSUPPORTED;
-    if (can && path != 1)
-      return run_tiled(points, num_points, batch, n, num_point_dim, g, max_num_points_in_voxel,
-                       max_voxels, vp, voxels, coords, num_points_per_voxel, num_voxels, coors_batched,
-                       workspace, s, path != 2);  // the library's choice (path 0) is the gather form
-  }
-  return run_sort_path<float>(points, num_points, batch, max_points, num_point_dim, g, max_num_points_in_voxel,
-                              max_voxels, voxels, coords, num_points_per_voxel, num_voxels, coors_batched, workspace, s);
+  if (wave_applicable(c, -1, wp)) return run_wave(c, wp, p.variant);
+  if (wave3d_applicable(c, -1, wp)) return run_wave(c, wp, 0, 0, true);
+  if (tiled_applicable(c, vp)) return run_tiled(c, vp, true);
+  return run_sort_path(c);
 }
 
 extern "C" int64_t pd3_hard_voxelize_index_list_entries(int batch, int64_t max_points) {
@@ -743,26 +753,14 @@ extern "C" int pd3_hard_voxelize_index(const float* points, const int32_t* num_p
                                        int32_t* point_list, int32_t* coords, int32_t* num_points_per_voxel,
                                        int32_t* num_voxels, int32_t* coors_batched, void* workspace,
                                        size_t workspace_bytes, void* stream) {
-  VoxGrid g;
-  if (!points || !vox_span || !point_list || !coords || !num_points_per_voxel || !num_voxels || !workspace)
-    return PD3_EINVAL;
-  if (batch <= 0 || max_points <= 0 || max_points >= ((int64_t)1 << 31) || num_point_dim < 3 ||
-      max_num_points_in_voxel <= 0 || max_voxels <= 0)
-    return PD3_EINVAL;
-  if (!make_grid(voxel_size, point_cloud_range, g)) return PD3_EINVAL;
-  if (workspace_bytes < pd3_hard_voxelize_workspace(batch, max_points, num_point_dim, voxel_size, point_cloud_range,
-                                                    max_num_points_in_voxel, max_voxels))
-    return PD3_EWORKSPACE;
-  hipStream_t s = static_cast<hipStream_t>(stream);
+  VoxCall<float> c{points, num_points, batch, max_points, num_point_dim, {}, max_num_points_in_voxel, max_voxels,
+                   nullptr, coords, num_points_per_voxel, num_voxels, coors_batched, workspace,
+                   static_cast<hipStream_t>(stream)};
+  if (const int rc = vox_check(c, vox_span && point_list, voxel_size, point_cloud_range, 0, workspace_bytes))
+    return rc;
   VwPlan wp;
-  if (wave_applicable(g, max_points, num_point_dim, max_num_points_in_voxel, max_voxels, batch, -1, wp))
-    return run_wave(points, num_points, batch, max_points, num_point_dim, g, max_num_points_in_voxel, max_voxels, wp,
-                    nullptr, coords, num_points_per_voxel, num_voxels, coors_batched, workspace, s, 1, 0, false, vox_span,
-                    point_list);
-  if (wave3d_applicable(g, max_points, num_point_dim, max_num_points_in_voxel, max_voxels, batch, -1, wp))
-    return run_wave(points, num_points, batch, max_points, num_point_dim, g, max_num_points_in_voxel, max_voxels, wp,
-                    nullptr, coords, num_points_per_voxel, num_voxels, coors_batched, workspace, s, 0, 0, true, vox_span,
-                    point_list);
+  if (wave_applicable(c, -1, wp)) return run_wave(c, wp, kVwPriority, 0, false, vox_span, point_list);
+  if (wave3d_applicable(c, -1, wp)) return run_wave(c, wp, 0, 0, true, vox_span, point_list);
   return PD3_EUNSUPPORTED;  // (the tiled and sort forms keep no per-voxel index list: run pd3_hard_voxelize)
 }
 
@@ -787,18 +785,12 @@ extern "C" int pd3_hard_voxelize_f64(const double* points, const int32_t* num_po
                                      int32_t* num_points_per_voxel, int32_t* num_voxels,
                                      int32_t* coors_batched, void* workspace, size_t workspace_bytes,
                                      void* stream) {
-  VoxGrid g;
-  if (!points || !voxels || !coords || !num_points_per_voxel || !num_voxels || !workspace) return PD3_EINVAL;
-  if (batch <= 0 || max_points <= 0 || max_points >= ((int64_t)1 << 31) || num_point_dim < 3 ||
-      max_num_points_in_voxel <= 0 || max_voxels <= 0)
-    return PD3_EINVAL;
-  if (!make_grid(voxel_size, point_cloud_range, g)) return PD3_EINVAL;
-  if (workspace_bytes < pd3_hard_voxelize_workspace(batch, max_points, num_point_dim, voxel_size, point_cloud_range,
-                                                    max_num_points_in_voxel, max_voxels))
-    return PD3_EWORKSPACE;
-  return run_sort_path<double>(points, num_points, batch, max_points, num_point_dim, g, max_num_points_in_voxel,
-                               max_voxels, voxels, coords, num_points_per_voxel, num_voxels, coors_batched, workspace,
-                               static_cast<hipStream_t>(stream));
+  VoxCall<double> c{points, num_points, batch, max_points, num_point_dim, {}, max_num_points_in_voxel, max_voxels,
+                    voxels, coords, num_points_per_voxel, num_voxels, coors_batched, workspace,
+                    static_cast<hipStream_t>(stream)};
+  if (const int rc = vox_check(c, voxels != nullptr, voxel_size, point_cloud_range, 0, workspace_bytes))
+    return rc;
+  return run_sort_path(c);
 }
 
 extern "C" int pd3_version(void) { return 200; }

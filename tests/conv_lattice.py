@@ -292,7 +292,7 @@ class Family:
 # ---- the families ----------------------------------------------------------------------------------------------------------
 # tile = (output rows, output columns, output channels per workgroup, input channels per trip)
 FAMILIES = {f.name: f for f in [
-    # conv3x3.hip:31-33 kCvCo = 64, kCvCi = 8; :385-395 the launcher's tiles: 2x128 / 4x64 / 1x128 / 2x64, else 4x32 (any map)
+    # conv3x3.hip:31-33 kCvCo = 64, kCvCi = 8; :383-393 the launcher's tiles: 2x128 / 4x64 / 1x128 / 2x64, else 4x32 (any map)
     Family("direct_s1", "conv3x3_bias_relu", "pack_conv3x3_weight", "supported", "pd3_conv3x3_bias_relu", (4, 32, 64, 8),
            "conv3x3.hip:31-33,385-389", "nchw3"),
     Family("direct_s2", "conv3x3_bias_relu", "pack_conv3x3_weight", "supported", "pd3_conv3x3_bias_relu", (4, 32, 64, 8),
@@ -331,7 +331,7 @@ FAMILIES = {f.name: f for f in [
            (4, 64, 16, 16), "conv_patch.hip:29-31,265", "patch", cin0=16, cout0=16, opts=dict(mode=2)),
     Family("patch3", "patch_conv_bias_relu", "pack_patch_weight", "patch_supported", "pd3_patch_conv_bias_relu",
            (4, 64, 4, 16), "conv_patch.hip:29-31,265", "patch", cin0=16, cout0=4, opts=dict(mode=3)),
-    # conv_patch_x3.hip:34-36 kPxPix = 256, kPxM = 128, kPxKC = 32; mode 0: a wave's 32 pixels share an output row (:353)
+    # conv_patch_x3.hip:34-36 kPxPix = 256, kPxM = 128, kPxKC = 32; mode 0: a wave's 32 pixels share an output row (:354)
     Family("patch0_x3", "patch_conv_x3_bias_relu", "pack_patch_weight_x3", "patch_x3_supported",
            "pd3_patch_conv_x3_bias_relu", (8, 32, 128, 16), "conv_patch_x3.hip:34-36,353", "patch", bar="x3", cin0=16,
            cout0=128, pitch_ok=False, opts=dict(mode=0), extra_channels=((16, 1024),)),
@@ -341,9 +341,9 @@ FAMILIES = {f.name: f for f in [
     Family("patch2_x3", "patch_conv_x3_bias_relu", "pack_patch_weight_x3", "patch_x3_supported",
            "pd3_patch_conv_x3_bias_relu", (4, 64, 64, 32), "conv_patch_x3.hip:34-36", "patch", bar="x3", cin0=32,
            cout0=64, opts=dict(mode=2), extra_channels=((32, 1024),)),
-    # conv3x3.hip:269-270 kGcCi = 4, kGcR x kGcW = 8 x 128 pixels, one group per workgroup
+    # conv3x3.hip:267-268 kGcCi = 4, kGcR x kGcW = 8 x 128 pixels, one group per workgroup
     Family("grouped", "grouped_conv3x3_small", "pack_grouped_weight", "grouped_small_supported",
-           "pd3_grouped_conv3x3_small_slice", (8, 128, 4, 4), "conv3x3.hip:269-270", "grouped", cin0=4, cout0=1,
+           "pd3_grouped_conv3x3_small_slice", (8, 128, 4, 4), "conv3x3.hip:267-268", "grouped", cin0=4, cout0=1,
            pitch_ok=False),
     # conv_f16.hip:35-44 kCfCols = 32, kCfKc = 16, CfShape: M = 64 MB channels, R = 16 rows
     Family("f16_t64", "conv3x3_f16_bias_relu", "pack_conv3x3_f16_weight", "f16_supported", "pd3_conv3x3_f16_bias_relu",
@@ -369,15 +369,15 @@ FAMILIES = {f.name: f for f in [
     Family("s2_f16", "conv3x3_s2_f16_bias_relu", "pack_conv3x3_f16_weight", "s2_f16_supported",
            "pd3_conv3x3_s2_f16_bias_relu", (8, 32, 128, 16), "conv_f16.hip:354-362", "f16s2", bar="f16", cin0=16, cout0=128,
            stride=2, out_f16=True, opts=dict(tile=128)),
-    # conv_f16.hip:928 tiles of 8 x 32 pixels, one group of 64 channels per block
+    # conv_f16.hip:922 tiles of 8 x 32 pixels, one group of 64 channels per block
     Family("grouped_f16", "grouped_conv3x3_small_f16", "pack_grouped_weight_f16", "-", "pd3_grouped_conv3x3_small_f16",
-           (8, 32, 4, 64), "conv_f16.hip:928", "groupedf16", bar="f16", cin0=64, cout0=1),
+           (8, 32, 4, 64), "conv_f16.hip:922", "groupedf16", bar="f16", cin0=64, cout0=1),
     Family("grouped_f16_gm", "grouped_conv3x3_small_f16", "pack_grouped_weight_f16", "-",
-           "pd3_grouped_conv3x3_small_f16_gm", (8, 32, 4, 64), "conv_f16.hip:769", "groupedf16", bar="f16", cin0=64, cout0=1,
+           "pd3_grouped_conv3x3_small_f16_gm", (8, 32, 4, 64), "conv_f16.hip:767", "groupedf16", bar="f16", cin0=64, cout0=1,
            opts=dict(group_major_in=True)),
-    # conv3x3.hip:416-423 the fused first layer's tiles: 2 x 128 / 2 x 64, else 4 x 32
+    # conv3x3.hip:414-421 the fused first layer's tiles: 2 x 128 / 2 x 64, else 4 x 32
     Family("scatter_f32", "scatter_conv3x3_bias_relu", "pack_conv3x3_weight", "scatter_conv_supported",
-           "pd3_scatter_conv3x3_bias_relu", (4, 32, 64, 8), "conv3x3.hip:416-423", "scatter", stride=2),
+           "pd3_scatter_conv3x3_bias_relu", (4, 32, 64, 8), "conv3x3.hip:414-421", "scatter", stride=2),
     Family("scatter_f16_t64", "scatter_conv3x3_s2_f16_bias_relu", "pack_conv3x3_f16_weight",
            "scatter_conv_s2_f16_supported", "pd3_scatter_conv3x3_s2_f16_bias_relu", (8, 32, 64, 16), "conv_f16.hip:354-362",
            "scatter", bar="f16", cin0=16, cout0=64, stride=2, out_f16=True, opts=dict(tile=64)),
@@ -706,7 +706,7 @@ OOB = 0x7ffffff0  # bf16x3.hpp:33 kPxOob: the buffer offset no tensor may reach
 
 
 def patch_x3_bytes_ok(mode, batch, cin, cout, ctot, h, w, w_valid):
-    """conv_patch_x3.hip:375-380."""
+    """conv_patch_x3.hip:376-381."""
     if mode == 0:
         ho, wo, nmt, steps, plane = h // 2, w // 2, cout // 128, 2 * (cin // 16), (h // 2) * (w // 2)
     elif mode == 1:

@@ -173,7 +173,7 @@ def test_winograd43_restatement_is_the_convolution(cin):
 
 def test_bf16x3_predicates_carry_the_launchers_byte_clause():
     """The 2 GB operand clause (32-bit buffer offsets) of the two bf16x3 kernels cannot be exercised with real buffers:
-    the predicates against a restatement of conv_patch_x3.hip:375-380 / conv_s2_x3.hip:269-275.  A predicate may be
+    the predicates against a restatement of conv_patch_x3.hip:376-381 / conv_s2_x3.hip:269-275.  A predicate may be
     stricter than its launcher (it does not know w_valid), never looser."""
     seen_false = 0
     for batch in (1, 16, 84, 85, 86, 128, 341, 342, 1 << 20):

@@ -127,7 +127,7 @@ def test_lattice_straddles_every_dispatch_clause():
              ((16, 16, 27), (16, 16, 28)),                                # kernel_volume <= 27
              ((16, 16, 3), (16, 24, 3)), ((16, 32, 3), (16, 48, 3)),      # cout in (16, 32, 64, 128)
              ((5, 16, 3), (5, 24, 3)), ((5, 16, 3), (5, 8, 3)),           # cout % 16
-             ((5, 128, 3), (5, 112, 3)), ((16, 48, 3), (16, 64, 3)),      # the switch's default: goto valu_path
+             ((5, 128, 3), (5, 112, 3)), ((16, 48, 3), (16, 64, 3)),      # cout / 16 not in (1, 2, 4, 8): the VALU kernel
              ((16, 64, 3), (16, 112, 3)), ((5, 64, 3), (5, 112, 3)),      # cout <= 64: one or two columns per lane
              ((32, 16, 3), (48, 16, 3)), ((32, 16, 3), (16, 16, 3))]      # cin % 32: eight or four channels per lane
     for a, b in pairs:
