@@ -229,7 +229,15 @@ int pd3_pillar_feature_net_path(const float *voxels, const int32_t *num_points, 
  * the point cloud itself: points [frames, points_per_frame, D], list_stride = rows of point_list per frame
  * (= max_points of the voxelizer call), coors [num_pillars, 4], pillars_per_frame = max_voxels.  Bit-identical to
  * pd3_hard_voxelize + pd3_pillar_feature_net.  Serves the two-layer 32 / 64 net with up to 32 points of 4 / 5
- * floats per pillar and pillars_per_frame a multiple of 8; other shapes return -3 (run the pair). */
+ * floats per pillar and pillars_per_frame a multiple of 8; other shapes return -3 (run the pair), and so do
+ * list_stride at or above 2^24 (a span's start, a position in a frame's row of the list, travels in 24 bits) and
+ * points_per_frame at or above 2^24 (a conservative bound: point indices are read from the list at their full 32 bits,
+ * but a list that names every point of such a frame once would not fit the row).
+ * The entry reads no device memory, so two bounds are the caller's to keep (pd3_hard_voxelize_index keeps both):
+ *   - coors' x and y cells lie in [0, 65536): the kernel carries them in 16 + 16 bits.  A grid with more than
+ *     65 536 cells along x or y gets wrong pillar centres -- run the pair there;
+ *   - a span's count is already capped at max_points: the kernel reads min(count, max_points) points and the cluster
+ *     mean divides by that, where pd3_pillar_feature_net divides by the num_points it is given. */
 int pd3_pillar_feature_net_indexed(const float *points, int64_t points_per_frame, const int32_t *vox_span,
                                    const int32_t *point_list, int64_t list_stride, const int32_t *coors,
                                    int64_t num_pillars, int pillars_per_frame, int max_points, int num_point_dim,

@@ -123,6 +123,10 @@ class PillarFeatureNet(nn.Module):
         self.vx, self.vy = float(voxel_size[0]), float(voxel_size[1])
         self.x_offset = self.vx / 2 + point_cloud_range[0]
         self.y_offset = self.vy / 2 + point_cloud_range[1]
+        # cells along x and y as the voxelizer counts them (voxelize_op.cc:97-102: round((max - min) / size) on fp32
+        # operands, half away from zero like std::round), for forward_indexed
+        vs32, pr32 = np.asarray(voxel_size, np.float32), np.asarray(point_cloud_range, np.float32)
+        self.grid_xy = tuple(int(math.floor(float((pr32[3 + a] - pr32[a]) / vs32[a]) + 0.5)) for a in range(2))
         self.max_num_points_in_voxel = max_num_points_in_voxel
         self._folded = None
 
@@ -148,8 +152,10 @@ class PillarFeatureNet(nn.Module):
 
     def forward_indexed(self, points, vox_span, point_list, coors):
         """forward() reading the pillars' points through the voxelizer's index (HardVoxelizer.index) from the point
-        cloud [B, N, D] itself; None for shapes the indexed kernel does not serve.  Same bytes as forward()."""
-        if len(self.pfn_layers) != 2:
+        cloud [B, N, D] itself; None for shapes the indexed kernel does not serve.  Same bytes as forward().
+        The indexed kernel carries a pillar's (x, y) cell in 16 + 16 bits and never sees the grid, so a grid with more
+        than 65 536 cells along x or y is answered with None here (the caller runs the pair); no host sync."""
+        if len(self.pfn_layers) != 2 or max(self.grid_xy) > _ve.INDEXED_MAX_AXIS_CELLS:
             return None
         sig = _param_signature(self)
         if self.training or self._folded is None or self._folded[0] != sig:

@@ -10,7 +10,8 @@
 // Padded rows (k >= num_points) are all identical after the reference's mask multiply (a zero input
 // row -> relu(shift)), so ONE pad row is evaluated and included in the max, as the reference's max over
 // all P rows does.  BatchNorm arrives folded (scale, shift).  fmaf is explicit (library builds with
-// -ffp-contract=off); results match the torch fp32 statement within 1e-4 (tests assert 1e-3 abs).
+// -ffp-contract=off); results match the torch fp32 statement within 1e-4 (tests/test_scatter_pfn_gpu.py asserts 1e-3 abs;
+// tests/pfn_lattice.py holds every form to the fp64 reference bit for bit on dyadic values and within a derived bound).
 #include "../../include/paddle3d_amd.h"
 #include "common.hpp"
 
@@ -1085,10 +1086,14 @@ extern "C" int pd3_pillar_feature_net_indexed(const float* points, int64_t point
     return PD3_EINVAL;
   PfnArgs a = pfn_args(nullptr, nullptr, coors, num_pillars, max_points, num_point_dim, voxel_center_dims, vx, vy, vz,
                        x_offset, y_offset, z_offset, w1, scale1, shift1, c1, w2, scale2, shift2, c2, out);
-  // the shapes of the packed kernel, whole chunks per frame, grid coordinates that fit 16 bits, pillar ids the fp32 frame
-  // lookup is exact for
+  // the shapes of the packed kernel, whole chunks per frame, pillar ids the fp32 frame lookup is exact for, list
+  // positions that fit the 24 bits a span's start travels in (load_span: list_stride), and with them frames whose points
+  // a list row of that length can name once each (points_per_frame: conservative, the point indices themselves are read
+  // at 32 bits).  NOT checked, because the entry never sees
+  // the grid or the spans (reading them would be a host sync): x and y cells below 2^16 (load_span packs them into
+  // 16 + 16 bits) and counts already capped at max_points -- the caller's to keep, see the header
   if (!(pfn_packed_ok(a) && pillars_per_frame % kPkPillars == 0 && num_pillars % pillars_per_frame == 0 &&
-        num_pillars < ((int64_t)1 << 22)))
+        num_pillars < ((int64_t)1 << 22) && points_per_frame < ((int64_t)1 << 24) && list_stride < ((int64_t)1 << 24)))
     return PD3_EUNSUPPORTED;
   a.points = points;
   a.n_pts = points_per_frame;

@@ -14,6 +14,9 @@ from ._common import check, lib, ptr, require_gpu, stream_ptr
 __all__ = ["pillar_feature_net", "pillar_feature_net_indexed", "hard_vfe", "voxel_mean", "fold_batchnorm"]
 
 
+INDEXED_MAX_AXIS_CELLS = 1 << 16  # pillar_feature_net_indexed: x and y cells travel in 16 bits each
+
+
 def fold_batchnorm(gamma, beta, mean, var, eps):
     scale = gamma / torch.sqrt(var + eps)
     return scale.contiguous(), (beta - mean * scale).contiguous()
@@ -56,7 +59,12 @@ def pillar_feature_net_indexed(points, vox_span, point_list, coors, max_points, 
     """pillar_feature_net on the voxelizer's index instead of a padded [M, P, D] tensor (pd3_pillar_feature_net_indexed):
     points [B, N, D], vox_span [B, V, 2] / point_list from ops.voxelize.hard_voxelize_index_batch, coors [B * V, 4].
     Returns [B * V, C2] -- the same bytes as hard_voxelize_batch + pillar_feature_net -- or None for shapes the
-    indexed kernel does not serve (the caller then runs the pair)."""
+    indexed kernel does not serve (the caller then runs the pair).
+    Bounds the entry cannot check, the caller's to keep: coors' x and y cells below INDEXED_MAX_AXIS_CELLS (the kernel
+    carries them in 16 + 16 bits and never sees the grid; PillarFeatureNet.forward_indexed answers None for a larger
+    grid), and every span's count already capped at max_points (the cluster mean divides by the count it is given).
+    N at or above 2^24 is refused by the entry (-3 -> None): a span's start, a position in a list row of N entries,
+    travels in 24 bits."""
     pts = require_gpu(points, "pillar_feature_net_indexed")
     sp = require_gpu(vox_span, "pillar_feature_net_indexed", torch.int32)
     pl = require_gpu(point_list, "pillar_feature_net_indexed", torch.int32)
@@ -90,6 +98,10 @@ def hard_vfe(voxels, num_points, coors, voxel_size, point_cloud_range, w1, scale
 
 
 def voxel_mean(voxels, num_points):
+    """VoxelMean.forward (voxel_encoder.py:44-57): the sum over all P rows divided by num_points, [M, P, D] -> [M, D].
+    A row with num_points == 0 holds what the reference's fp32 division gives: sum / 0, i.e. NaN for a zero sum (the
+    all-zero padding row of a fixed-shape batch) and +-inf for a nonzero one; num_points above P divides the P-row sum by
+    num_points all the same."""
     v = require_gpu(voxels, "voxel_mean")
     n = require_gpu(num_points, "voxel_mean", torch.int32)
     m, p, d = v.shape

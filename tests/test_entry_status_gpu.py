@@ -120,11 +120,11 @@ def pfn_path(t, m=M, center_dims=3, c1=32, c2=64, path=0, null=False):
                                              g("out"), path, stream_ptr(t["out"].device))
 
 
-def pfn_indexed(t, m=M, per_frame=M // 2, list_stride=N):
+def pfn_indexed(t, m=M, per_frame=M // 2, list_stride=N, n=N):
     from paddle3d_amd.ops._common import lib, ptr, stream_ptr
 
     g = lambda k: ptr(t[k])  # noqa: E731
-    return lib().pd3_pillar_feature_net_indexed(g("pts"), N, g("span"), g("plist"), list_stride, g("coors"), m, per_frame, MAXP,
+    return lib().pd3_pillar_feature_net_indexed(g("pts"), n, g("span"), g("plist"), list_stride, g("coors"), m, per_frame, MAXP,
                                                 D, 3, 0.5, 0.5, 8.0, 0.25, 0.25, 1.0, g("w1"), g("s1"), g("b1"), 32, g("w2"),
                                                 g("s2"), g("b2"), 64, g("out"), stream_ptr(t["out"].device))
 
@@ -142,3 +142,9 @@ def test_pfn_indexed_statuses(pfn_bufs):
     assert pfn_indexed(pfn_bufs, m=2 * (chunk + 1), per_frame=chunk + 1) == EUNSUPPORTED
     assert pfn_indexed(pfn_bufs, list_stride=0) == EINVAL
     assert pfn_indexed(pfn_bufs, m=0) == 0
+    # a span's start (a position in the list row) travels in 24 bits: a list row that long, and a frame whose points such a
+    # row could not name once each, are refused before anything is read
+    assert pfn_indexed(pfn_bufs, n=1 << 24) == EUNSUPPORTED
+    assert pfn_indexed(pfn_bufs, list_stride=1 << 24) == EUNSUPPORTED
+    assert pfn_indexed(pfn_bufs, n=1 << 24, list_stride=0) == EINVAL  # ranges before shapes
+    assert pfn_indexed(pfn_bufs) == 0  # the case itself is served (all spans empty: zeros out)
