@@ -15,8 +15,28 @@ LIB_PATH = os.path.join(_HERE, "lib", "libpaddle3d_amd.so")
 c_f32p = C.c_void_p
 c_i32p = C.c_void_p
 
-# symbol -> (restype, argtypes); mirrors include/paddle3d_amd.h one to one
-_SIGNATURES = {
+# ONE table: symbol -> (restype, argtypes, scenarios).  restype / argtypes mirror include/paddle3d_amd.h one to one
+# (tests/test_abi.py holds every row to the header); `scenarios` is the bare name of the test module whose guarded
+# scenarios (tests/guarded.py: Protocol) have to reach the entry point -- that module's last test fails until one does.
+# A new entry point is one row in the block of the module that holds its scenarios.
+ENTRY_POINTS = {}
+
+
+def _block(scenarios, rows):
+    for name, (res, args) in rows.items():
+        if name in ENTRY_POINTS:
+            raise ValueError(f"{name} has a row in the block of {ENTRY_POINTS[name][2]} "
+                             f"and another in that of {scenarios}")
+        ENTRY_POINTS[name] = (res, args, scenarios)
+
+
+def symbols(module=None):
+    """Every entry point's name in table order, or those whose guarded scenarios live in tests/<module>.py."""
+    return tuple(name for name, row in ENTRY_POINTS.items() if module is None or row[2] == module)
+
+
+# the first models' ops: voxelization, pillar encoders, NMS, post-processing, point ops, sparse and dense convolutions
+_block("test_memory_safety_gpu", {
     "pd3_version": (C.c_int, []),
     "pd3_target_arch": (C.c_char_p, []),
     "pd3_hard_voxelize_workspace": (C.c_size_t, [C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
@@ -225,14 +245,10 @@ _SIGNATURES = {
     "pd3_grouped_conv3x3_small_slice": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                                   C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                                   C.c_void_p]),
-}
+})
 
-SYMBOLS = tuple(_SIGNATURES)
-
-# Voxel R-CNN's RoI head (csrc/roi_head.hip).  A table of its own ON PURPOSE: tests/test_memory_safety_gpu.py fails for
-# any name in SYMBOLS that has no scenario in that file, and these entry points have theirs in
-# tests/test_memory_safety_roi_gpu.py, which ends in the same completeness assertion over SYMBOLS_ROI.
-_SIGNATURES_ROI = {
+# Voxel R-CNN's RoI head (csrc/roi_head.hip)
+_block("test_memory_safety_roi_gpu", {
     "pd3_voxel_pool": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 7 + [C.c_float] + [C.c_int] * 5 + [C.c_void_p] * 2),
     "pd3_roi_grid_points": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int] +
                             [C.c_void_p] * 3),
@@ -241,119 +257,82 @@ _SIGNATURES_ROI = {
     "pd3_class_agnostic_nms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_float,
                                          C.c_void_p, C.c_int, C.c_float, C.c_int] + [C.c_void_p] * 5 +
                                [C.c_size_t, C.c_void_p]),
-}
+})
 
-SYMBOLS_ROI = tuple(_SIGNATURES_ROI)
-
-# The final SeparateHead convolutions with per-group channel counts (csrc/conv3x3.hip).  A table of its own for the same
-# reason: its guarded scenarios and the completeness assertion over SYMBOLS_HEAD are in tests/test_grouped_counts_gpu.py.
-# (Tables per test file do not scale: the plan is ONE table whose entries name the test module that holds their scenarios,
-# with each completeness assertion filtering on that name; it needs the two existing memory-safety files changed together.)
-_SIGNATURES_HEAD = {
+# the final SeparateHead convolutions with per-group channel counts (csrc/conv3x3.hip)
+_block("test_grouped_counts_gpu", {
     "pd3_grouped_conv3x3_small_counts_slice": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                                          C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                                          C.c_int, C.c_void_p]),
-}
+})
 
-SYMBOLS_HEAD = tuple(_SIGNATURES_HEAD)
-
-# PV-RCNN's keypoint branch and RoI head (csrc/pvrcnn.hip).  The third table of this kind, for the same reason: its
-# guarded scenarios and the completeness assertion over SYMBOLS_PVRCNN are in tests/test_memory_safety_pvrcnn_gpu.py
-# (a copy of the RoI file's protocol; under the one-table plan above it becomes a module name in its entries).
-_SIGNATURES_PVRCNN = {
+# PV-RCNN's keypoint branch and RoI head (csrc/pvrcnn.hip)
+_block("test_memory_safety_pvrcnn_gpu", {
     "pd3_stack_sa_pool": (C.c_int, [C.c_void_p] * 11 + [C.c_int] * 5 + [C.c_float, C.c_int] + [C.c_void_p] * 2),
     "pd3_bev_interpolate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_int] * 4 + [C.c_float] * 5 +
                             [C.c_void_p] * 2),
-}
+})
 
-SYMBOLS_PVRCNN = tuple(_SIGNATURES_PVRCNN)
-
-# CaDDN's frustum-to-voxel and map-to-BEV stage (csrc/caddn.hip).  The fourth table of this kind, for the same reason:
-# its guarded scenarios and the completeness assertion over SYMBOLS_CADDN are in tests/test_memory_safety_caddn_gpu.py.
+# CaDDN's frustum-to-voxel and map-to-BEV stage (csrc/caddn.hip)
 _CADDN_GRID = [C.c_int] * 3 + [C.c_void_p] * 2 + [C.c_int, C.c_double, C.c_double]  # grid, pc_min, voxel_size, mode, depths
 _CADDN_IN = [C.c_void_p] * 5 + [C.c_int] * 5 + _CADDN_GRID  # features, logits, calibration, image_shape, B, C, D, h, w
-_SIGNATURES_CADDN = {
+_block("test_memory_safety_caddn_gpu", {
     "pd3_frustum_grid": (C.c_int, [C.c_void_p] * 3 + [C.c_int] + _CADDN_GRID + [C.c_int] + [C.c_void_p] * 2),
     "pd3_frustum_to_voxel_workspace": (C.c_size_t, [C.c_int] * 5),
     "pd3_frustum_to_voxel": (C.c_int, _CADDN_IN + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "pd3_frustum_to_bev_workspace": (C.c_size_t, [C.c_int] * 7),
     "pd3_frustum_to_bev": (C.c_int, _CADDN_IN + [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
                                                                     C.c_void_p]),
-}
+})
 
-SYMBOLS_CADDN = tuple(_SIGNATURES_CADDN)
-
-# BEVFormer's encoder attention (csrc/bevformer.hip).  The fifth table of this kind, for the same reason: its guarded
-# scenarios and the completeness assertion over SYMBOLS_BEVFORMER are in tests/test_memory_safety_bevformer_gpu.py.
-_SIGNATURES_BEVFORMER = {
+# BEVFormer's encoder attention (csrc/bevformer.hip)
+_block("test_memory_safety_bevformer_gpu", {
     "pd3_bevformer_point_sampling": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_void_p] * 5),
     "pd3_bevformer_sca": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 9 + [C.c_void_p] * 2),
     "pd3_bevformer_tsa": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 7 + [C.c_void_p] * 2),
-}
+})
 
-SYMBOLS_BEVFORMER = tuple(_SIGNATURES_BEVFORMER)
-
-# BEVFormer's decoder, head and NMS-free decode (csrc/bevformer_decoder.hip).  The sixth table of this kind, for the same
-# reason: its guarded scenarios and the completeness assertion over SYMBOLS_BEVFORMER_DEC are in
-# tests/test_memory_safety_bevformer_dec_gpu.py.
-_SIGNATURES_BEVFORMER_DEC = {
+# BEVFormer's decoder, head and NMS-free decode (csrc/bevformer_decoder.hip)
+_block("test_memory_safety_bevformer_dec_gpu", {
     "pd3_mha_forward": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_float] + [C.c_void_p] * 2),
     "pd3_bevformer_dec_ca": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 8 + [C.c_void_p] * 2),
     "pd3_nms_free_decode": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_double, C.c_int] + [C.c_void_p] * 5),
-}
+})
 
-SYMBOLS_BEVFORMER_DEC = tuple(_SIGNATURES_BEVFORMER_DEC)
-
-# PETR / PETRv2's head (csrc/petr.hip).  The seventh table of this kind, for the same reason: its guarded scenarios and
-# the completeness assertion over SYMBOLS_PETR are in tests/test_memory_safety_petr_gpu.py.
-_SIGNATURES_PETR = {
+# PETR / PETRv2's head (csrc/petr.hip)
+_block("test_memory_safety_petr_gpu", {
     "pd3_mha_stream_forward": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_float] + [C.c_void_p] * 2),
     "pd3_petr_coords3d": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.c_double, C.c_void_p, C.c_int] + [C.c_void_p] * 4),
-}
+})
 
-SYMBOLS_PETR = tuple(_SIGNATURES_PETR)
-
-# SqueezeSegV3's SAC block and range projection (csrc/squeezeseg.hip).  The eighth table of this kind, for the same
-# reason: its guarded scenarios and the completeness assertion over SYMBOLS_SQSEG are in
-# tests/test_memory_safety_squeezeseg_gpu.py.
-_SIGNATURES_SQSEG = {
+# SqueezeSegV3's SAC block and range projection (csrc/squeezeseg.hip)
+_block("test_memory_safety_squeezeseg_gpu", {
     "pd3_sac_isk_forward": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 4 + [C.c_void_p] * 2),
     "pd3_range_project": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p] + [C.c_int] * 3 + [C.c_double] * 2 +
                           [C.c_void_p] * 8 + [C.c_size_t, C.c_void_p]),
-}
+})
 
-SYMBOLS_SQSEG = tuple(_SIGNATURES_SQSEG)
-
-# BEVFusion's Anchor3DHead (csrc/anchor3d_head.hip).  The ninth table of this kind, for the same reason: its guarded
-# scenarios and the completeness assertion over SYMBOLS_ANCHOR3D are in tests/test_memory_safety_anchor3d_gpu.py.
+# BEVFusion's Anchor3DHead (csrc/anchor3d_head.hip)
 _A3D_CFG = [C.c_int] * 2 + [C.c_float] * 4 + [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p]  # nms_pre .. stream
-_SIGNATURES_ANCHOR3D = {
+_block("test_memory_safety_anchor3d_gpu", {
     "pd3_anchor3d_head_workspace": (C.c_size_t, [C.c_int] * 7),
     "pd3_anchor3d_head_forward": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 7 + _A3D_CFG),
     "pd3_anchor3d_get_bboxes": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 6 + _A3D_CFG),
-}
+})
 
-SYMBOLS_ANCHOR3D = tuple(_SIGNATURES_ANCHOR3D)
-
-# The sparse first backbone layer as one launch (csrc/pillar_conv_span.hip).  The tenth table of this kind, for the same
-# reason: its guarded scenario and the completeness assertion over SYMBOLS_SPAN are in tests/test_pillar_conv_span_gpu.py.
-_SIGNATURES_SPAN = {
+# the sparse first backbone layer as one launch (csrc/pillar_conv_span.hip)
+_block("test_pillar_conv_span_gpu", {
     "pd3_pillar_conv_span_x3": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 3 +
                                 [C.c_int] + [C.c_void_p] * 2),
-}
+})
 
-SYMBOLS_SPAN = tuple(_SIGNATURES_SPAN)
-
-# IA-SSD's fused set abstraction and box decode (csrc/iassd.hip).  The eleventh table of this kind, for the same reason:
-# its guarded scenarios and the completeness assertion over SYMBOLS_IASSD are in tests/test_memory_safety_iassd_gpu.py.
-_SIGNATURES_IASSD = {
+# IA-SSD's fused set abstraction and box decode (csrc/iassd.hip)
+_block("test_memory_safety_iassd_gpu", {
     "pd3_sa_msg_pool": (C.c_int, [C.c_void_p] * 12 + [C.c_int] * 6 + [C.c_float, C.c_int, C.c_void_p, C.c_int64,
                                                                      C.c_void_p]),
     "pd3_iassd_decode": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int] +
                          [C.c_void_p] * 2),
-}
-
-SYMBOLS_IASSD = tuple(_SIGNATURES_IASSD)
+})
 
 
 class Paddle3DAmdError(RuntimeError):
@@ -367,12 +346,7 @@ def lib() -> C.CDLL:
             f"{LIB_PATH} not found: build it with `python -m paddle3d_amd.build` "
             "(there is no CPU / PyTorch fallback for the HIP ops)")
     handle = C.CDLL(LIB_PATH)
-    for name, (res, args) in (list(_SIGNATURES.items()) + list(_SIGNATURES_ROI.items()) +
-                              list(_SIGNATURES_HEAD.items()) + list(_SIGNATURES_PVRCNN.items()) +
-                              list(_SIGNATURES_CADDN.items()) + list(_SIGNATURES_BEVFORMER.items()) +
-                              list(_SIGNATURES_BEVFORMER_DEC.items()) + list(_SIGNATURES_PETR.items()) +
-                              list(_SIGNATURES_SQSEG.items()) + list(_SIGNATURES_ANCHOR3D.items()) +
-                              list(_SIGNATURES_SPAN.items()) + list(_SIGNATURES_IASSD.items())):
+    for name, (res, args, _) in ENTRY_POINTS.items():
         try:
             fn = getattr(handle, name)
         except AttributeError as e:  # pragma: no cover

@@ -26,13 +26,19 @@ What is NOT intercepted: tensors that come out of torch operators (`cat`, `stack
 carry no stale bytes; an overrun past one of them is not seen.  The library hands such tensors to kernels as inputs
 only (every output and workspace is one of the patched calls), and inputs are `const` in the ABI.
 
-`launch_ledger()` counts the calls of every C-ABI symbol made through the cached `paddle3d_amd._lib.lib()` handle.
+`launch_ledger(handle, symbols)` counts the calls of the named C-ABI symbols made through a `paddle3d_amd._lib.lib()`
+handle.
+
+`Protocol` is the three-pass run every memory-safety file holds its scenarios to (plain, fill 0x00, fill 0xFF) and the
+completeness assertion over the entry points whose table rows name that file; tests/test_guarded_cpu.py shows, on fake
+ops, that each of its assertions fails when it should.
 """
 from __future__ import annotations
 
 import contextlib
 from dataclasses import dataclass
 
+import numpy as np
 import torch
 
 G = 1 << 20          # bytes of guard band on each side; a multiple of 512 (see the module docstring)
@@ -216,16 +222,13 @@ def guarded(fill: int, device="cuda"):
 
 
 @contextlib.contextmanager
-def launch_ledger(handle=None, symbols=None):
-    """Count the calls of every C-ABI symbol made through the cached `lib()` handle: yields {symbol: calls}.
+def launch_ledger(handle, symbols):
+    """Count the calls of the C-ABI `symbols` made through `handle` (`paddle3d_amd._lib.lib()`): yields {symbol: calls}.
+    There is no default name set: a caller that asserts "nothing else ran" says which names it watches
+    (`_lib.symbols()` is all of them, `_lib.symbols(module)` one block of the table).
 
     A counting Python wrapper is put on the handle as an instance attribute under each name; it calls the original
-    function object (with its argtypes / restype) through.  The originals are put back on exit, also on an exception.
-    `handle` / `symbols` default to `paddle3d_amd._lib.lib()` / `paddle3d_amd._lib.SYMBOLS`."""
-    if handle is None:
-        from paddle3d_amd import _lib
-
-        handle, symbols = _lib.lib(), _lib.SYMBOLS
+    function object (with its argtypes / restype) through.  The originals are put back on exit, also on an exception."""
     calls = {name: 0 for name in symbols}
     originals = {name: getattr(handle, name) for name in symbols}
 
@@ -245,3 +248,127 @@ def launch_ledger(handle=None, symbols=None):
     finally:
         for name, fn in originals.items():
             setattr(handle, name, fn)
+
+
+def _host(v):
+    if isinstance(v, np.ndarray):
+        v = torch.from_numpy(np.ascontiguousarray(v))
+    return v.detach().contiguous().cpu()
+
+
+def _bits(t):
+    return t.reshape(-1).view(torch.uint8)
+
+
+def _nontrivial(t):
+    """The number of elements that are neither 0 nor -1 (this code base's "no neighbour") nor NaN."""
+    x = t.reshape(-1)
+    x = x[~torch.isnan(x)].double() if x.dtype.is_floating_point else x.long()
+    return int(((x != 0) & (x != -1)).sum())
+
+
+class Protocol:
+    """One memory-safety file's scenarios, its ledger and the assertions they are held to.
+
+    `module` is the file's bare name: the ledger counts `_lib.symbols(module)`, the names whose table rows say their
+    scenarios live here.  A scenario is a function that builds seeded inputs and returns `(inputs, call)`; `call()`
+    returns the dict of specified outputs (tensors or ndarrays), in which `__trivial_ok__` may name the outputs that
+    are legally all 0 / -1.  `tolerant` maps (scenario, output suffix) to {dtype: relative bound of max(|plain|, 1)}
+    for the outputs that are documented as order dependent; everything else compares bit for bit.  `before_pass()`
+    runs ahead of every pass, outside the guard and the ledger; `may_allocate_nothing` names the scenarios whose
+    guarded passes need not allocate.  `handle` / `symbols` replace the library and its table (the CPU self-test)."""
+
+    def __init__(self, module, tag, device, tolerant=None, before_pass=None, may_allocate_nothing=(), handle=None,
+                 symbols=None):
+        self.module, self.tag, self.device = module, tag, torch.device(device)
+        self.tolerant, self.before_pass, self.may_allocate_nothing = tolerant or {}, before_pass, set(may_allocate_nothing)
+        self.handle, self.symbols = handle, symbols
+        self.scenarios = {}
+        self.ledger = {}   # symbol -> calls, summed over the guarded 0xFF pass of every scenario that ran
+        self.ran = set()
+
+    def scenario(self, fn):
+        self.scenarios[fn.__name__] = fn
+        return fn
+
+    def _count(self, calls):
+        for sym, n in calls.items():
+            self.ledger[sym] = self.ledger.get(sym, 0) + n
+
+    def run(self, name, mode):
+        """One pass of a scenario: (specified outputs on the host, guard damage, names of changed inputs, calls per
+        symbol, names of the outputs that may be trivial)."""
+        if self.handle is None:
+            from paddle3d_amd import _lib
+
+            self.handle, self.symbols = _lib.lib(), _lib.symbols(self.module)
+        if self.before_pass is not None:
+            self.before_pass()
+        print(f"[{self.tag}] {name}: {mode}", flush=True)
+        ctx = contextlib.nullcontext(None) if mode == "plain" else guarded(int(mode, 16), self.device)
+        with ctx as g, launch_ledger(self.handle, self.symbols) as calls:
+            inputs, call = self.scenarios[name]()
+            before = {k: v.clone() for k, v in inputs.items()}
+            outs = call()
+            if self.device.type == "cuda":
+                torch.cuda.synchronize()
+            damage = g.check() if g is not None else []
+            trivial_ok = outs.pop("__trivial_ok__", set())
+            host = {k: _host(v) for k, v in outs.items()}
+            changed = [k for k, v in inputs.items() if not torch.equal(_bits(_host(v)), _bits(_host(before[k])))]
+            if g is not None and self.device.type == "cuda":  # every guarded tensor has the caching allocator's alignment
+                assert all(buf.data_ptr() % 512 == 0 for buf, _, _, _ in g.blocks)
+            assert g is None or len(g.blocks) > 0 or name in self.may_allocate_nothing, f"{name} [{mode}]: nothing allocated"
+        return host, damage, changed, {k: v for k, v in calls.items() if v}, trivial_ok
+
+    def check_scenario(self, name):
+        ref, damage, changed, calls, trivial_ok = self.run(name, "plain")
+        assert damage == [] and changed == [], f"{name} [plain]: inputs written: {changed}"
+        assert ref, f"{name}: no outputs"
+        for k, v in ref.items():  # 4. the specified outputs are not trivial
+            if k not in trivial_ok:
+                assert v.numel() > 0 and _nontrivial(v) > 0, f"{name}: output {k} {tuple(v.shape)} is empty or all 0 / -1"
+        for mode in ("0x00", "0xFF"):
+            got, damage, changed, calls_g, _ = self.run(name, mode)
+            # 1. no store outside an output or a workspace
+            assert damage == [], f"{name} [{mode}]: " + "; ".join(str(d) for d in damage)
+            # 3. inputs are const
+            assert changed == [], f"{name} [{mode}]: inputs written: {changed}"
+            # 2. no result depends on what its buffer held before
+            assert set(got) == set(ref), (name, mode, set(got) ^ set(ref))
+            for k, want in ref.items():
+                have = got[k]
+                assert have.shape == want.shape and have.dtype == want.dtype, (name, mode, k, have.shape, want.shape)
+                tols = next((t for (scn, key), t in self.tolerant.items() if scn == name and k.endswith(key)), None)
+                if tols is not None:
+                    tol = tols[want.dtype]  # (a dtype without a bound of its own is an error, not a default)
+                    err = float((have.double() - want.double()).abs().max())
+                    bound = tol * max(float(want.double().abs().max()), 1.0)
+                    assert bool(torch.isfinite(have).all()) and err <= bound, f"{name} [{mode}]: {k}: {err} > {bound}"
+                    continue
+                diff = (_bits(have) != _bits(want)).nonzero().reshape(-1)
+                if diff.numel():
+                    first = int(diff[0]) // have.element_size()
+                    raise AssertionError(
+                        f"{name} [{mode}]: output {k} {tuple(have.shape)} {have.dtype} depends on the previous contents "
+                        f"of memory: {diff.numel()} bytes differ from the plain run, first at element {first} "
+                        f"(plain {want.reshape(-1)[first].item()!r}, guarded {have.reshape(-1)[first].item()!r})")
+            assert set(calls_g) == set(calls), (f"{name} [{mode}]: other entry points ran than in the plain run: "
+                                                f"{sorted(set(calls_g) ^ set(calls))}")
+        self._count(calls_g)
+        self.ran.add(name)
+
+    def check_complete(self, required, count=None):
+        """Every name of `required` (`count` of them, where the file states a literal count) is reached by a scenario.
+        Scenarios that did not run in this process (the test selected alone, or with -k) are run here in their plain
+        form under the ledger, so the assertion never depends on test selection."""
+        for name in self.scenarios:
+            if name not in self.ran:
+                self._count(self.run(name, "plain")[3])
+                self.ran.add(name)
+        required = list(required)
+        assert count is None or len(required) == count, (self.module, len(required), count)
+        missing = [s for s in required if not self.ledger.get(s)]
+        assert not missing, (f"{len(missing)} of the {len(required)} required entry points of {self.module} are reached "
+                             f"by no scenario: {missing}.  This is intended to fail for a symbol newly added to the "
+                             f"table: add a scenario to tests/{self.module}.py that calls it.")

@@ -1,4 +1,5 @@
-"""The C-ABI library loads without a GPU and exports exactly what include/paddle3d_amd.h declares."""
+"""The C-ABI library loads without a GPU and exports exactly what include/paddle3d_amd.h declares; the loader's one table
+(paddle3d_amd._lib.ENTRY_POINTS) agrees with the header name for name and parameter for parameter."""
 import ctypes as C
 import os
 import re
@@ -33,8 +34,75 @@ def test_loader_binds_every_symbol(built):
     L = _lib.lib()
     assert L.pd3_version() >= 100
     assert L.pd3_target_arch() == b"gfx950"
-    for name in _lib.SYMBOLS:
+    for name in _lib.symbols():
         assert getattr(L, name).argtypes is not None
+
+
+SCALARS = {"float": C.c_float, "double": C.c_double, "int": C.c_int, "int64_t": C.c_int64, "uint32_t": C.c_uint32,
+           "size_t": C.c_size_t}
+# the table's blocks: the names whose guarded scenarios live in tests/<module>.py (a count for the large first one)
+BLOCKS = {
+    "test_memory_safety_gpu": 102,
+    "test_memory_safety_roi_gpu": {"pd3_voxel_pool", "pd3_roi_grid_points", "pd3_rcnn_decode_boxes",
+                                   "pd3_class_agnostic_nms_workspace", "pd3_class_agnostic_nms"},
+    "test_grouped_counts_gpu": {"pd3_grouped_conv3x3_small_counts_slice"},
+    "test_memory_safety_pvrcnn_gpu": {"pd3_stack_sa_pool", "pd3_bev_interpolate"},
+    "test_memory_safety_caddn_gpu": {"pd3_frustum_grid", "pd3_frustum_to_voxel_workspace", "pd3_frustum_to_voxel",
+                                     "pd3_frustum_to_bev_workspace", "pd3_frustum_to_bev"},
+    "test_memory_safety_bevformer_gpu": {"pd3_bevformer_point_sampling", "pd3_bevformer_sca", "pd3_bevformer_tsa"},
+    "test_memory_safety_bevformer_dec_gpu": {"pd3_mha_forward", "pd3_bevformer_dec_ca", "pd3_nms_free_decode"},
+    "test_memory_safety_petr_gpu": {"pd3_mha_stream_forward", "pd3_petr_coords3d"},
+    "test_memory_safety_squeezeseg_gpu": {"pd3_sac_isk_forward", "pd3_range_project"},
+    "test_memory_safety_anchor3d_gpu": {"pd3_anchor3d_head_workspace", "pd3_anchor3d_head_forward",
+                                        "pd3_anchor3d_get_bboxes"},
+    "test_pillar_conv_span_gpu": {"pd3_pillar_conv_span_x3"},
+    "test_memory_safety_iassd_gpu": {"pd3_sa_msg_pool", "pd3_iassd_decode"},
+}
+
+
+def _ctype(decl, returned=False):
+    """The ctypes type of a C parameter or return type as the header writes it."""
+    if "*" in decl:
+        return C.c_char_p if returned and decl.split("*")[0].split() == ["const", "char"] else C.c_void_p
+    return SCALARS[decl.split()[0]]
+
+
+def test_entry_points_match_the_header(built):
+    """Every row of the one table against its declaration: the same names, the return type and every parameter mapped
+    to its ctypes type, and as many argtypes on the bound function."""
+    from paddle3d_amd import _lib
+
+    hdr = open(os.path.join(ROOT, "include", "paddle3d_amd.h")).read()
+    hdr = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", hdr, flags=re.S))
+    declared = {name: (ret.strip(), [" ".join(q.split()) for q in params.split(",")])
+                for ret, name, params in re.findall(r"([\w \*]+?)\b(pd3_\w+)\s*\(([^;{)]*)\)\s*;", hdr)}
+    assert set(declared) == set(_lib.ENTRY_POINTS), set(declared) ^ set(_lib.ENTRY_POINTS)
+    assert len(re.findall(r"\bpd3_\w+\s*\(", hdr)) == len(declared)  # nothing declared twice, nothing the pattern missed
+    L = _lib.lib()
+    for name, (res, args, _) in _lib.ENTRY_POINTS.items():
+        ret, params = declared[name]
+        if params == ["void"]:
+            params = []
+        assert res is _ctype(ret, returned=True), (name, ret, res)
+        assert len(args) == len(params) == len(getattr(L, name).argtypes), (name, len(args), len(params))
+        for i, (q, a) in enumerate(zip(params, args)):
+            assert a is _ctype(q), (name, i, q, a)
+
+
+def test_entry_points_name_the_module_of_their_scenarios():
+    from paddle3d_amd import _lib
+
+    assert len(_lib.symbols()) == len(_lib.ENTRY_POINTS) == 131
+    assert list(dict.fromkeys(row[2] for row in _lib.ENTRY_POINTS.values())) == list(BLOCKS)
+    for module, want in BLOCKS.items():
+        assert os.path.isfile(os.path.join(ROOT, "tests", module + ".py")), module
+        names = _lib.symbols(module)
+        assert len(names) == want if isinstance(want, int) else set(names) == want, (module, names)
+    assert _lib.symbols("test_memory_safety_squeezeseg_gpu") == ("pd3_sac_isk_forward", "pd3_range_project")  # in order
+    assert _lib.symbols("test_no_such_module") == ()
+    with pytest.raises(ValueError, match="pd3_version has a row"):  # a second row for a name is refused
+        _lib._block("test_memory_safety_roi_gpu", {"pd3_version": (C.c_int, [])})
+    assert _lib.ENTRY_POINTS["pd3_version"][2] == "test_memory_safety_gpu"
 
 
 def test_library_is_gfx950_code_object(built):

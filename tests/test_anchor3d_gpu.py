@@ -23,9 +23,13 @@ import make_anchor3d_golden as mk  # noqa: E402
 import test_anchor3d_cpu as cpu  # noqa: E402
 from test_anchor3d_cpu import golden  # noqa: E402,F401  (fixture)
 
+from paddle3d_amd import _lib  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda", 0)
 F32 = np.float32
+# the table's first block (patch convolution, per-class NMS, ...): what the head runs besides its own entry points
+FIRST_BLOCK = _lib.symbols("test_memory_safety_gpu")
 
 
 def _t(a):
@@ -265,7 +269,7 @@ def test_module_forward_runs_the_patch_convolution():
                            bbox_coder=dict(code_size=7), test_cfg=dict(nms_pre=50, max_num=20, score_thr=0.3, nms_thr=0.1))
     head = head.to(DEV).eval()
     x = torch.randn(2, 32, 4, 10, device=DEV)
-    with launch_ledger() as base, torch.no_grad():
+    with launch_ledger(_lib.lib(), FIRST_BLOCK) as base, torch.no_grad():
         maps = head([x])
     assert base["pd3_patch_conv_bias_relu"] == 3
     for m, conv in zip(maps, (head.conv_cls, head.conv_reg, head.conv_dir_cls)):
@@ -318,10 +322,8 @@ def test_refused_shapes_return_none_and_the_module_falls_back(golden):  # noqa: 
     tag = "kitti"
     head = cpu.build_head(tag).to(DEV)
     x, metas = _t(an.golden_inputs(tag)), [{}] * 2
-    with launch_ledger() as base, torch.no_grad():
-        from paddle3d_amd import _lib
-
-        with launch_ledger(_lib.lib(), _lib.SYMBOLS_ANCHOR3D) as calls:
+    with launch_ledger(_lib.lib(), FIRST_BLOCK) as base, torch.no_grad():
+        with launch_ledger(_lib.lib(), _lib.symbols("test_memory_safety_anchor3d_gpu")) as calls:
             head.test_cfg = dict(head.test_cfg, nms_pre=-1)  # all 210 anchors: taken by the kernels
             n_all = [len(r[1]) for r in head.forward_get_bboxes([x], metas)]
             assert calls["pd3_anchor3d_head_forward"] == 1
@@ -337,8 +339,6 @@ def test_refused_shapes_return_none_and_the_module_falls_back(golden):  # noqa: 
 
 
 def test_no_host_synchronisation_and_launch_counts(golden):  # noqa: F811
-    from paddle3d_amd import _lib
-
     tag = "nus"
     head = cpu.build_head(tag).to(DEV)
     x, metas = _t(an.golden_inputs(tag)), [{}] * 2
@@ -349,7 +349,7 @@ def test_no_host_synchronisation_and_launch_counts(golden):  # noqa: F811
         torch.cuda.synchronize()
         torch.cuda.set_sync_debug_mode("error")
         try:
-            with launch_ledger(_lib.lib(), _lib.SYMBOLS_ANCHOR3D) as calls:
+            with launch_ledger(_lib.lib(), _lib.symbols("test_memory_safety_anchor3d_gpu")) as calls:
                 a = head.forward_get_bboxes([x], metas, fused="force", return_padded=True)
                 b = head.get_bboxes(*maps, metas, return_padded=True)
         finally:
@@ -357,6 +357,7 @@ def test_no_host_synchronisation_and_launch_counts(golden):  # noqa: F811
     assert calls == {"pd3_anchor3d_head_workspace": 2, "pd3_anchor3d_head_forward": 1, "pd3_anchor3d_get_bboxes": 1}
     same_results(a, cpu.restated(tag), "lazy")
     cpu.check_padded(golden, tag, [_n(t) for t in b])
-    with launch_ledger() as base, torch.no_grad():  # the lazy path runs no convolution and no per-class NMS call
+    # the lazy path runs no convolution and no per-class NMS call
+    with launch_ledger(_lib.lib(), FIRST_BLOCK) as base, torch.no_grad():
         head.forward_get_bboxes([x], metas, fused="force", return_padded=True)
     assert not any(base.values()), {k: v for k, v in base.items() if v}

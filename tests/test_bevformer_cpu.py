@@ -1,14 +1,13 @@
 """BEVFormer's encoder attention on the CPU: the NumPy restatement of the three entry points
 (tests/golden/bevformer_numpy.py) against what the reference's own Python computed (tests/golden/python_bevformer.npz),
-the fused spatial cross-attention against the reference's rebatch / scatter algorithm, SYMBOLS_BEVFORMER against the
-header, the refusal statuses, and the maker's conditions on the committed file.
+the fused spatial cross-attention against the reference's rebatch / scatter algorithm,
+the refusal statuses, and the maker's conditions on the committed file.
 
 Bounds: the ones the maker stored, 4 x the largest error of the reference's own fp32 run against its fp64 run (one fp32
 ulp of the largest output as a floor).  reference_points_cam: that bound over the points in front of the camera, and the
 same rule on a relative scale for the components behind it (u = x / 1e-5, about 1e5 in size).  The masks are compared
 bit for bit: the maker keeps every u, v 1e-4 and every depth a factor of 10 away from the comparisons' edges."""
 import os
-import re
 import sys
 
 import numpy as np
@@ -16,7 +15,6 @@ import pytest
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 sys.path.insert(0, os.path.join(HERE, "golden"))
 import bevformer_numpy as bn  # noqa: E402
 import make_bevformer_golden as mk  # noqa: E402
@@ -135,32 +133,6 @@ def test_fused_sca_equals_the_rebatch_form(golden, expf, tag):
     assert np.array_equal(got.view(np.uint32), sca.view(np.uint32))
     seen = ps[3] > 0
     assert np.abs(sca[seen]).min(-1).max() > 0 and not sca[~seen].any()  # misses are exactly zero
-
-
-def test_symbols_match_the_header():
-    from paddle3d_amd import _lib, build
-
-    hdr = open(os.path.join(ROOT, "include", "paddle3d_amd.h")).read()
-    first, last = hdr.index("BEVFormer's encoder attention"), hdr.index("CaDDN's frustum-to-voxel")
-    assert first < last
-    assert set(re.findall(r"\b(pd3_\w+)\s*\(", hdr[last:])) == set(_lib.SYMBOLS_CADDN)  # CaDDN's section is still last
-    hdr = hdr[first:last]
-    declared = set(re.findall(r"\b(pd3_\w+)\s*\(", hdr))
-    assert declared == set(_lib.SYMBOLS_BEVFORMER) and len(declared) == 3
-    build.build()
-    L = _lib.lib()
-    for name in _lib.SYMBOLS_BEVFORMER:
-        res, args = _lib._SIGNATURES_BEVFORMER[name]
-        m = re.search(r"(\w+)\s+%s\s*\(([^;]*)\)\s*;" % name, hdr)
-        assert m, name
-        params = [p.strip() for p in m.group(2).split(",")]
-        assert len(params) == len(args) == len(getattr(L, name).argtypes), (name, len(params), len(args))
-        assert m.group(1) == "int" and res is _lib.C.c_int
-        for p, a in zip(params, args):
-            assert a is (_lib.C.c_void_p if "*" in p else _lib.C.c_int), (name, p)
-    others = (set(_lib.SYMBOLS) | set(_lib.SYMBOLS_ROI) | set(_lib.SYMBOLS_HEAD) | set(_lib.SYMBOLS_PVRCNN) |
-              set(_lib.SYMBOLS_CADDN))
-    assert not set(_lib.SYMBOLS_BEVFORMER) & others
 
 
 def test_refusals_need_no_gpu():

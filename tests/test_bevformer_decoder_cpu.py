@@ -3,14 +3,13 @@
 (tests/golden/python_bevformer_decoder.npz) -- the attention outputs, and, with the restatement standing in for the
 device ops inside the modules of paddle3d_amd.bevformer_head, the layer, the decoder's states and reference points and
 the head's outputs; the restated decode against get_bboxes; the threshold loop against a transcription; the modules'
-state-dict keys; SYMBOLS_BEVFORMER_DEC against the header; the refusal statuses; the maker's conditions on the
+state-dict keys; the refusal statuses; the maker's conditions on the
 committed file.
 
 Bounds: the ones the maker stored, 4 x the largest error of the reference's own fp32 run against its fp64 run (one fp32
 ulp of the largest output as a floor).  Labels, rows and counts of the decode are compared exactly: the maker keeps
 every score, threshold and centre further from a decision than those bounds."""
 import os
-import re
 import sys
 
 import numpy as np
@@ -18,7 +17,6 @@ import pytest
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 sys.path.insert(0, os.path.join(HERE, "golden"))
 import bevformer_decoder_numpy as dn  # noqa: E402
 import make_bevformer_decoder_golden as mk  # noqa: E402
@@ -290,32 +288,6 @@ def _decoder_cfg(tag):
     cfg = dict(mk.head_cfg(tag)["transformer"]["decoder"])
     cfg.pop("type_name")
     return cfg
-
-
-def test_symbols_match_the_header():
-    from paddle3d_amd import _lib, build
-
-    hdr = open(os.path.join(ROOT, "include", "paddle3d_amd.h")).read()
-    first, last = hdr.index("BEVFormer's decoder, head and NMS-free decode"), hdr.index("BEVFormer's encoder attention")
-    assert first < last
-    hdr = hdr[first:last]
-    declared = set(re.findall(r"\b(pd3_\w+)\s*\(", hdr))
-    assert declared == set(_lib.SYMBOLS_BEVFORMER_DEC) and len(declared) == 3
-    build.build()
-    L = _lib.lib()
-    kinds = {"float": _lib.C.c_float, "double": _lib.C.c_double, "int": _lib.C.c_int}
-    for name in _lib.SYMBOLS_BEVFORMER_DEC:
-        res, args = _lib._SIGNATURES_BEVFORMER_DEC[name]
-        m = re.search(r"(\w+)\s+%s\s*\(([^;]*)\)\s*;" % name, hdr)
-        assert m, name
-        params = [p.strip() for p in m.group(2).split(",")]
-        assert len(params) == len(args) == len(getattr(L, name).argtypes), (name, len(params), len(args))
-        assert m.group(1) == "int" and res is _lib.C.c_int
-        for p, a in zip(params, args):
-            assert a is (_lib.C.c_void_p if "*" in p else kinds[p.split()[0]]), (name, p)
-    others = (set(_lib.SYMBOLS) | set(_lib.SYMBOLS_ROI) | set(_lib.SYMBOLS_HEAD) | set(_lib.SYMBOLS_PVRCNN) |
-              set(_lib.SYMBOLS_CADDN) | set(_lib.SYMBOLS_BEVFORMER))
-    assert not set(_lib.SYMBOLS_BEVFORMER_DEC) & others
 
 
 def test_refusals_need_no_gpu():

@@ -328,7 +328,7 @@ def test_refused_shapes_fall_back():
     from paddle3d_amd import _lib, bevformer_head as bh
     from paddle3d_amd.ops import bevformer_decoder as ops
 
-    names = _lib.SYMBOLS_BEVFORMER_DEC + ("pd3_ms_deform_attn_forward",)
+    names = _lib.symbols("test_memory_safety_bevformer_dec_gpu") + ("pd3_ms_deform_attn_forward",)
     B, Q = 1, 20
     sh, lsi, S = dn.md.level_layout([[3, 4]])
     sh, lsi = _t(sh), _t(lsi)
@@ -400,7 +400,7 @@ def test_launch_counts(golden):
 
     tag = "c"
     names = ("pd3_mha_forward", "pd3_bevformer_dec_ca", "pd3_nms_free_decode")
-    symbols = _lib.SYMBOLS_BEVFORMER_DEC + ("pd3_ms_deform_attn_forward",)
+    symbols = _lib.symbols("test_memory_safety_bevformer_dec_gpu") + ("pd3_ms_deform_attn_forward",)
     bev = _t(mk.inputs(tag)["bev_embed"])
     h = head(tag, True)
     with torch.no_grad():

@@ -290,6 +290,7 @@ def test_refused_shapes_fall_back():
     from paddle3d_amd import _lib, bevformer
     from paddle3d_amd.ops import bevformer as ops
 
+    with_msda = _lib.symbols("test_memory_safety_bevformer_gpu") + ("pd3_ms_deform_attn_forward",)
     torch.manual_seed(5)
     B, Q, cams, D = 1, 20, 2, 4
     sh, lsi, S = _levels([[3, 4]])
@@ -310,7 +311,7 @@ def test_refused_shapes_fall_back():
                                                   fused=fused).eval().to(DEV)
             tsa = bevformer.TemporalSelfAttention(embed_dims=E, num_heads=M, num_levels=1, num_points=P,
                                                   fused=fused).eval().to(DEV)
-            with torch.no_grad(), launch_ledger(_lib.lib(), _lib.SYMBOLS_BEVFORMER + ("pd3_ms_deform_attn_forward",)) as n:
+            with torch.no_grad(), launch_ledger(_lib.lib(), with_msda) as n:
                 outs.append((sca(q, feats, feats, reference_points_cam=ref_cam, bev_mask=mask, spatial_shapes=sh,
                                  level_start_index=lsi),
                              tsa(q, queue, queue, reference_points=ref_2d, spatial_shapes=_t(bev_sh),
@@ -352,19 +353,20 @@ def test_launch_counts(golden):
     enc = encoder(tag, True)
     args, kw = encoder_inputs(golden, tag)
     names = ("pd3_bevformer_point_sampling", "pd3_bevformer_sca", "pd3_bevformer_tsa")
+    with_msda = _lib.symbols("test_memory_safety_bevformer_gpu") + ("pd3_ms_deform_attn_forward",)
     with torch.no_grad():
-        with launch_ledger(_lib.lib(), _lib.SYMBOLS_BEVFORMER) as n:
+        with launch_ledger(_lib.lib(), _lib.symbols("test_memory_safety_bevformer_gpu")) as n:
             enc(*args, **kw)
         assert [n[k] for k in names] == [1, mk.LAYERS, mk.LAYERS], dict(n)
         q, pos, prev = (_t(inp[k]) for k in ("bev_query", "bev_pos", "prev_bev"))
         ref_3d = enc.get_reference_points(*c["bev"], cpu.Z_RANGE, c["D"], "3d", c["B"], torch.float32, DEV)
         ref_cam, mask = enc.point_sampling(ref_3d, mk.PC_RANGE, kw["img_metas"])
         queue = torch.stack([prev, q], 1).reshape(c["B"] * 2, -1, mk.EMBED)
-        with launch_ledger(_lib.lib(), _lib.SYMBOLS_BEVFORMER + ("pd3_ms_deform_attn_forward",)) as n:
+        with launch_ledger(_lib.lib(), with_msda) as n:
             enc.layers[0](q, args[1], args[2], bev_pos=pos, ref_2d=_t(cpu.ref_2d(tag)), bev_h=kw["bev_h"], bev_w=kw["bev_w"],
                           spatial_shapes=kw["spatial_shapes"], level_start_index=kw["level_start_index"],
                           reference_points_cam=ref_cam, bev_mask=mask, prev_bev=queue)
         assert [n[k] for k in names] == [0, 1, 1] and n["pd3_ms_deform_attn_forward"] == 0, dict(n)
-        with launch_ledger(_lib.lib(), _lib.SYMBOLS_BEVFORMER + ("pd3_ms_deform_attn_forward",)) as n:
+        with launch_ledger(_lib.lib(), with_msda) as n:
             encoder(tag, False)(*args, **kw)
         assert [n[k] for k in names] == [1, 0, 0] and n["pd3_ms_deform_attn_forward"] == 2 * mk.LAYERS, dict(n)

@@ -162,7 +162,7 @@ def test_modules_reproduce_the_reference(golden, tag, fused):
     feats, logits = (_t(a) for a in mk.inputs(tag))
     m = _module(g, tag, fused)
     bd = _batch(g, tag)
-    with torch.no_grad(), launch_ledger(_lib.lib(), _lib.SYMBOLS_CADDN) as calls:
+    with torch.no_grad(), launch_ledger(_lib.lib(), _lib.symbols("test_memory_safety_caddn_gpu")) as calls:
         out = m(feats, logits, bd)
     assert bool(calls.get("pd3_frustum_to_bev")) == fused and bool(calls.get("pd3_frustum_to_voxel")) != fused
     assert out is bd["spatial_features"]
@@ -212,7 +212,7 @@ def test_refused_shapes_return_unsupported_and_the_module_falls_back(golden):
         if outs:
             m.load_state_dict(first.state_dict())
         first = m
-        with torch.no_grad(), launch_ledger(_lib.lib(), _lib.SYMBOLS_CADDN) as calls:
+        with torch.no_grad(), launch_ledger(_lib.lib(), _lib.symbols("test_memory_safety_caddn_gpu")) as calls:
             outs.append(m(feats, logits, _batch(g, tag)))
         assert calls.get("pd3_frustum_to_voxel") and not calls.get("pd3_frustum_to_bev")
     assert outs[0].shape == (2, 40, Y, X) and torch.equal(outs[0], outs[1]) and float(outs[0].abs().max()) > 0

@@ -258,7 +258,7 @@ def test_dispatchers_cover_every_kernel():
 
     gen = torch.Generator().manual_seed(20)
     torch.manual_seed(20)
-    with launch_ledger() as calls:
+    with launch_ledger(_lib.lib(), _lib.symbols("test_memory_safety_gpu")) as calls:
         # _Conv3x3: both strides, with and without w_valid, either side of WINOGRAD43_PP_MIN_CIN and of the pre-transformed
         # form's 8 blocks, the bf16x3 stride-2 kernel's cout <= 1024 bound (1152 falls back to the fp32 implicit GEMM)
         for cin, cout, stride, n, h, wv in [(8, 64, 1, 2, 9, 20), (60, 64, 1, 1, 5, 18), (64, 64, 1, 1, 9, 68), (64, 448, 1, 1, 3, 12),
@@ -366,7 +366,7 @@ def test_dispatchers_cover_every_kernel():
             head(torch.zeros(1, 64, 8, 18, device=DEV))
 
         reached = {k for k, v in calls.items() if v}
-    dense = sorted(s for s in _lib.SYMBOLS if DENSE_CONV.match(s))
+    dense = sorted(s for s in _lib.symbols("test_memory_safety_gpu") if DENSE_CONV.match(s))
     assert {f.symbol for f in L.FAMILIES.values() if f.kind != "scatter" or f.name != "scatter_sparse"} <= set(dense)
     missing = [s for s in dense if s not in reached and s not in NOT_DISPATCHED]
     assert not missing, f"dense convolution entry points no dispatcher reached: {missing}"

@@ -1,8 +1,8 @@
 """pd3_grouped_conv3x3_small_counts_slice (the final SeparateHead convolutions with every group's real channel count) against
 pd3_grouped_conv3x3_small_slice on zero padded weights and bias: the same bytes, the padded channels' +0.0 included, every
-byte of the slice written and nothing outside it.  The entry point has its own symbol table (paddle3d_amd._lib.SYMBOLS_HEAD):
-its scenario under guarded allocations (tests/guarded.py, the protocol of tests/test_memory_safety_gpu.py) and the
-completeness assertion over that table are at the end of this file."""
+byte of the slice written and nothing outside it.  The entry point's row in paddle3d_amd._lib.ENTRY_POINTS names this
+module: its scenario under guarded allocations (tests/guarded.py: Protocol) and the completeness assertion over the rows
+that name this module are at the end of this file."""
 import os
 import sys
 
@@ -10,7 +10,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from guarded import guarded, launch_ledger  # noqa: E402
+from guarded import Protocol  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -135,12 +135,13 @@ def test_center_head_slices_use_the_counts_form():
             assert torch.equal(a[name], b[name]), name
 
 
-_REACHED = {}
+P = Protocol("test_grouped_counts_gpu", "grouped-counts", "cuda")
 
 
-def _guarded_scenario():
-    """Seeded inputs (made outside the guard) and a call whose outputs are allocated inside it: a slice into a wider
-    tensor that the caller cleared, and a whole tensor the wrapper allocates (torch.empty: stale bytes under the guard)."""
+@P.scenario
+def counts_form():
+    """Seeded inputs and a call whose outputs are allocated under the guard: a slice into a wider tensor that the caller
+    cleared, and a whole tensor the wrapper allocates (torch.empty: stale bytes under the guard)."""
     from paddle3d_amd.ops import conv
 
     co, counts = COUNTS["mixed4"]
@@ -165,43 +166,11 @@ def _guarded_scenario():
 
 
 def test_counts_form_under_guarded_allocations():
-    from paddle3d_amd import _lib
-
-    inputs, call = _guarded_scenario()
-    clones = {k: v.clone() for k, v in inputs.items()}
-    runs = {}
-    for mode, fill in (("plain", None), ("fill00", 0x00), ("fillff", 0xFF)):
-        with launch_ledger(_lib.lib(), _lib.SYMBOLS_HEAD) as calls:
-            if fill is None:
-                outs = call()
-                torch.cuda.synchronize()
-                damage = []
-            else:
-                with guarded(fill) as g:
-                    outs = call()
-                    torch.cuda.synchronize()
-                    damage = g.check()
-        assert not damage, (mode, [str(d) for d in damage])
-        for k, v in inputs.items():
-            assert torch.equal(_bits(v), _bits(clones[k])), (mode, k, "an input changed")
-        runs[mode] = {k: v.cpu() for k, v in outs.items()}
-        for sym, c in calls.items():
-            _REACHED[sym] = _REACHED.get(sym, 0) + c
-    for k, want in runs["plain"].items():
-        assert bool(want.any()), k  # not trivial
-        for mode in ("fill00", "fillff"):
-            assert torch.equal(_bits(runs[mode][k]), _bits(want)), (mode, k, "depends on the previous contents of memory")
+    P.check_scenario("counts_form")
 
 
 def test_every_entry_point_of_symbols_head_is_exercised():
     """Runs last; runs the scenario itself when it was not selected."""
     from paddle3d_amd import _lib
 
-    if not _REACHED:
-        _, call = _guarded_scenario()
-        with launch_ledger(_lib.lib(), _lib.SYMBOLS_HEAD) as calls:
-            call()
-            torch.cuda.synchronize()
-        _REACHED.update(calls)
-    missing = [s for s in _lib.SYMBOLS_HEAD if not _REACHED.get(s)]
-    assert not missing, missing
+    P.check_complete(_lib.symbols("test_grouped_counts_gpu"), 1)

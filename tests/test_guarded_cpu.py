@@ -1,15 +1,19 @@
 """The guarded-allocation harness (tests/guarded.py) proves it can fail: small fake "ops" on the CPU, one per defect
-class the GPU memory-safety scenarios are meant to catch, plus the plumbing (argument forms, other devices, restore).
+class the GPU memory-safety scenarios are meant to catch, plus the plumbing (argument forms, other devices, restore);
+then the Protocol every memory-safety file runs its scenarios through, on a fake handle with two Python functions as
+entry points: each of its assertions fails, with its own message, on the defect it is there for.
 No GPU is needed; test_launch_ledger_on_the_real_handle loads the built libpaddle3d_amd.so (`python -m
 paddle3d_amd.build`), the same precondition as tests/test_abi.py."""
 import os
 import sys
+import types
 
+import numpy as np
 import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from guarded import G, PATTERN, guarded, launch_ledger  # noqa: E402
+from guarded import G, PATTERN, Protocol, guarded, launch_ledger  # noqa: E402
 
 
 def _bits(t):
@@ -241,9 +245,180 @@ def test_launch_ledger_on_the_real_handle():
 
     L = _lib.lib()
     orig = L.pd3_version
-    with launch_ledger() as calls:
-        assert set(calls) == set(_lib.SYMBOLS)
+    with launch_ledger(_lib.lib(), _lib.symbols("test_memory_safety_gpu")) as calls:
+        assert set(calls) == set(_lib.symbols("test_memory_safety_gpu"))
         v = L.pd3_version()
         assert _lib.lib().pd3_target_arch() == b"gfx950"
     assert calls["pd3_version"] == 1 and calls["pd3_target_arch"] == 1 and sum(calls.values()) == 2
     assert L.pd3_version is orig and L.pd3_version() == v and L.pd3_version.argtypes is not None
+
+
+# ---- the Protocol on fake entry points --------------------------------------------------------------------------------
+def _fake_protocol(**kw):
+    """A Protocol over a handle whose two "entry points" are Python functions on CPU tensors."""
+    h = types.SimpleNamespace(pd3_copy=lambda dst, src: dst.copy_(src),
+                              pd3_double=lambda dst, src: torch.mul(src, 2, out=dst))
+    return Protocol("fake_module", "protocol-self-test", "cpu", handle=h, symbols=("pd3_copy", "pd3_double"), **kw), h
+
+
+torch_empty = torch.empty  # the unpatched function: what a before_pass hook has to see
+
+
+def _x():
+    return torch.randn(6, 4, generator=torch.Generator().manual_seed(1))
+
+
+def _guarded_now(t):
+    """True for a tensor carved out of a guarded buffer (the fake defects below need the bands to write into)."""
+    return t.untyped_storage().nbytes() >= t.numel() * t.element_size() + 2 * G
+
+
+def test_protocol_passes_a_clean_scenario_and_counts_its_calls():
+    P, h = _fake_protocol()
+
+    @P.scenario
+    def clean():
+        inputs = dict(x=_x())
+
+        def call():
+            out, two = torch.empty(6, 4), torch.empty_like(inputs["x"])
+            h.pd3_copy(out, inputs["x"])
+            h.pd3_double(two, inputs["x"])
+            h.pd3_double(two, inputs["x"])
+            return dict(out=out, two=two.numpy(), none=torch.full((3,), -1, dtype=torch.int32), __trivial_ok__={"none"})
+
+        return inputs, call
+
+    P.check_scenario("clean")
+    assert P.ran == {"clean"} and P.ledger == {"pd3_copy": 1, "pd3_double": 2}  # the 0xFF pass's calls
+    host, damage, changed, calls, trivial_ok = P.run("clean", "0xFF")
+    assert torch.equal(host["out"], _x()) and torch.equal(host["two"], 2 * _x()) and trivial_ok == {"none"}
+    assert damage == [] and changed == [] and calls == {"pd3_copy": 1, "pd3_double": 2}
+    assert h.pd3_copy.__name__ == "<lambda>"  # the ledger's wrappers are gone
+
+
+def _defect(body, **kw):
+    """A Protocol with one scenario `bad` whose call() is body(handle, inputs)."""
+    P, h = _fake_protocol(**kw)
+
+    @P.scenario
+    def bad():
+        inputs = dict(x=_x())
+        return inputs, lambda: body(h, inputs)
+
+    return P
+
+
+def _overrun(h, inputs):  # one element past the output
+    out = torch.empty(6, 4)
+    h.pd3_copy(out, inputs["x"])
+    if _guarded_now(out):
+        for b in range(4):
+            _poke(out, out.numel() * 4 + b)
+    return dict(out=out)
+
+
+def _stale(h, inputs):  # the last row is never written
+    out = torch.empty(6, 4)
+    h.pd3_copy(out[:-1], inputs["x"][:-1])
+    return dict(out=out)
+
+
+def _writes_input(h, inputs):
+    out = torch.empty(6, 4)
+    h.pd3_copy(out, inputs["x"])
+    h.pd3_double(inputs["x"], inputs["x"])
+    return dict(out=out)
+
+
+def _trivial(h, inputs):
+    out, idx = torch.empty(6, 4), torch.full((5,), -1, dtype=torch.int32)
+    h.pd3_copy(out, inputs["x"])
+    return dict(out=out, idx=idx)
+
+
+def _other_symbols(h, inputs):  # another path under the guard than in production
+    out = torch.empty(6, 4)
+    if _guarded_now(out):
+        h.pd3_double(out, inputs["x"] / 2)
+    else:
+        h.pd3_copy(out, inputs["x"])
+    return dict(out=out)
+
+
+@pytest.mark.parametrize("body,message", [
+    (_overrun, r"bad \[0x00\]: allocation #0 \(6, 4\) torch.float32: tail guard damaged at byte \+0"),
+    (_stale, r"bad \[0x..\]: output out \(6, 4\) torch.float32 depends on the previous contents of memory: \d+ bytes differ "
+             r"from the plain run, first at element 2\d \(plain .*, guarded (0.0|nan)\)"),
+    (_writes_input, r"bad \[plain\]: inputs written: \['x'\]"),
+    (_trivial, r"bad: output idx \(5,\) is empty or all 0 / -1"),
+    (_other_symbols, r"bad \[0x00\]: other entry points ran than in the plain run: \['pd3_copy', 'pd3_double'\]"),
+], ids=["overrun", "stale", "writes_input", "trivial", "other_symbols"])
+def test_protocol_fails_each_defect_with_its_own_message(body, message):
+    P = _defect(body)
+    with pytest.raises(AssertionError, match=message):
+        P.check_scenario("bad")
+    assert P.ran == set() and P.ledger == {}  # a failed scenario counts for nothing
+
+
+def test_protocol_tolerance_and_allocation_rules():
+    def noisy(h, inputs):  # an order-dependent sum: the last bits differ from run to run
+        acc = torch.zeros(6, 4, dtype=torch.float64)
+        h.pd3_copy(acc, inputs["x"])
+        return dict(grad_acc=acc + (1e-9 if _guarded_now(acc) else 0.0))
+
+    with pytest.raises(AssertionError, match="depends on the previous contents"):
+        _defect(noisy).check_scenario("bad")
+    _defect(noisy, tolerant={("bad", "acc"): {torch.float64: 1e-8}}).check_scenario("bad")
+    with pytest.raises(AssertionError, match=r"bad \[0x00\]: grad_acc: 1\.0\d*e-09 > \d"):  # (relative to max |plain|)
+        _defect(noisy, tolerant={("bad", "acc"): {torch.float64: 1e-10}}).check_scenario("bad")
+    with pytest.raises(KeyError):  # a dtype without a bound of its own is an error, not a default
+        _defect(noisy, tolerant={("bad", "acc"): {torch.float32: 1e-4}}).check_scenario("bad")
+
+    def allocates_nothing(h, inputs):
+        return dict(n=np.array([3]))
+
+    with pytest.raises(AssertionError, match=r"bad \[0x00\]: nothing allocated"):
+        _defect(allocates_nothing).check_scenario("bad")
+    seen = []
+    P = _defect(allocates_nothing, may_allocate_nothing={"bad"}, before_pass=lambda: seen.append(torch.empty is torch_empty))
+    P.check_scenario("bad")
+    assert seen == [True] * 3  # the hook runs ahead of every pass, outside the guard
+
+
+def test_protocol_completeness():
+    P, h = _fake_protocol()
+
+    @P.scenario
+    def copies():
+        inputs = dict(x=_x())
+
+        def call():
+            out = torch.empty(6, 4)
+            h.pd3_copy(out, inputs["x"])
+            return dict(out=out)
+
+        return inputs, call
+
+    P.check_scenario("copies")
+    P.check_complete(["pd3_copy"], 1)
+    with pytest.raises(AssertionError, match=r"1 of the 2 required entry points of fake_module are reached by no scenario: "
+                                             r"\['pd3_double'\].*tests/fake_module.py"):
+        P.check_complete(["pd3_copy", "pd3_double"], 2)
+    with pytest.raises(AssertionError):  # the literal count a file states
+        P.check_complete(["pd3_copy"], 2)
+
+    @P.scenario
+    def doubles():
+        inputs = dict(x=_x())
+
+        def call():
+            out = torch.empty(6, 4)
+            h.pd3_double(out, inputs["x"])
+            return dict(out=out)
+
+        return inputs, call
+
+    assert P.ran == {"copies"}
+    P.check_complete(["pd3_copy", "pd3_double"], 2)  # runs what did not run, in its plain form
+    assert P.ran == {"copies", "doubles"} and P.ledger == {"pd3_copy": 1, "pd3_double": 1}

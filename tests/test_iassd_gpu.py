@@ -336,7 +336,7 @@ def test_whole_model_on_the_golden_input(fused):
     score_tol = float(g["e2e_batch_cls_preds_bound"]) / 4 + 2.0 ** -24
     from paddle3d_amd import _lib
 
-    with launch_ledger(_lib.lib(), _lib.SYMBOLS_IASSD) as calls:
+    with launch_ledger(_lib.lib(), _lib.symbols("test_memory_safety_iassd_gpu")) as calls:
         preds = m({"data": _t(g["data"]), "batch_size": mk.B}, as_list=True)
     _lists_equal(preds, g, "post", box_tol, score_tol)
     assert calls == {"pd3_sa_msg_pool": 8 if fused == "force" else 0, "pd3_iassd_decode": 1}
@@ -393,7 +393,7 @@ def test_refused_shapes_take_the_composition():
     assert [a.scale_is_fused(i) for i in range(3)] == [True, False, False]
     xyz, feats = torch.rand(2, 100, 3, device=DEV) * 4, torch.randn(2, 2, 100, device=DEV)
     from paddle3d_amd import _lib
-    with torch.no_grad(), launch_ledger(_lib.lib(), _lib.SYMBOLS_IASSD) as calls:
+    with torch.no_grad(), launch_ledger(_lib.lib(), _lib.symbols("test_memory_safety_iassd_gpu")) as calls:
         ra, rb = a(xyz, feats), b(xyz, feats)
     assert calls["pd3_sa_msg_pool"] == 1 and torch.equal(ra[0], rb[0])
     for x, y in zip(ra[1:], rb[1:]):

@@ -15,7 +15,6 @@ the model inside the run, so packed weights, plans and cached workspaces are all
 
 The last test asserts that the scenarios reach every kernel-launching entry point of the C ABI.
 """
-import contextlib
 import ctypes as C
 import os
 import sys
@@ -27,7 +26,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(HERE, "golden"))
-from guarded import guarded, launch_ledger  # noqa: E402
+from guarded import Protocol  # noqa: E402
 
 from paddle3d_amd import synth  # noqa: E402
 
@@ -35,7 +34,6 @@ pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda", 0)
 F32 = np.float32
 
-SCENARIOS = {}
 # outputs compared under a tolerance instead of bit for bit: (scenario, output suffix) -> {dtype: relative bound (of
 # max(|reference|, 1))}.  ms_deform_attn's grad_value is accumulated with float atomics ("may differ in the last bits from
 # run to run", paddle3d_amd.h); the bounds are the ones tests/test_ms_deform_attn_gpu.py::
@@ -44,13 +42,18 @@ SCENARIOS = {}
 # exact in any order, and compares bit for bit; assign_score_withk's backward has no atomics (its own test:
 # test_backward_reproducible) and is exact as well.
 TOLERANT = {("ms_deform_attn", "grad_value"): {torch.float32: 1e-4, torch.float64: 1e-10}}
-_LEDGER = {}   # symbol -> calls, summed over the guarded 0xFF pass of every scenario that ran
-_RAN = set()
 
 
-def scenario(fn):
-    SCENARIOS[fn.__name__] = fn
-    return fn
+def _probe_lds_atomic_order():
+    """The self-check is probed once per process: keep its launch out of whichever scenario runs first."""
+    from paddle3d_amd.ops import voxelize
+
+    voxelize.lds_atomic_order_ok(DEV)
+
+
+P = Protocol("test_memory_safety_gpu", "memory-safety", DEV, tolerant=TOLERANT, before_pass=_probe_lds_atomic_order,
+             may_allocate_nothing={"selfcheck_lds_atomic_order"})
+scenario = P.scenario
 
 
 def _t(a):
@@ -1266,84 +1269,9 @@ def selfcheck_lds_atomic_order():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-def _host(v):
-    if isinstance(v, np.ndarray):
-        v = torch.from_numpy(np.ascontiguousarray(v))
-    return v.detach().contiguous().cpu()
-
-
-def _bits(t):
-    return t.reshape(-1).view(torch.uint8)
-
-
-def _run(name, mode):
-    """One pass of a scenario: (specified outputs on the host, guard damage, names of changed inputs, ledger)."""
-    from paddle3d_amd.ops import voxelize
-
-    voxelize.lds_atomic_order_ok(DEV)  # probed once per process: keep its launch out of whichever scenario runs first
-    print(f"[memory-safety] {name}: {mode}", flush=True)
-    ctx = contextlib.nullcontext(None) if mode == "plain" else guarded(int(mode, 16), DEV)
-    with ctx as g, launch_ledger() as calls:
-        inputs, call = SCENARIOS[name]()
-        before = {k: v.clone() for k, v in inputs.items()}
-        outs = call()
-        torch.cuda.synchronize()
-        damage = g.check() if g is not None else []
-        trivial_ok = outs.pop("__trivial_ok__", set())
-        host = {k: _host(v) for k, v in outs.items()}
-        changed = [k for k, v in inputs.items() if not torch.equal(_bits(_host(v)), _bits(_host(before[k])))]
-        if g is not None:  # every guarded tensor has the caching allocator's alignment
-            assert all(buf.data_ptr() % 512 == 0 for buf, _, _, _ in g.blocks)
-            assert len(g.blocks) > 0 or name == "selfcheck_lds_atomic_order"
-    return host, damage, changed, {k: v for k, v in calls.items() if v}, trivial_ok
-
-
-def _nontrivial(t):
-    x = t.reshape(-1)
-    if x.dtype.is_floating_point:
-        x = x[~torch.isnan(x)].double()
-    else:
-        x = x.long()
-    return int(((x != 0) & (x != -1)).sum())
-
-
-@pytest.mark.parametrize("name", list(SCENARIOS))
+@pytest.mark.parametrize("name", list(P.scenarios))
 def test_scenario(name):
-    ref, damage, changed, calls, trivial_ok = _run(name, "plain")
-    assert damage == [] and changed == [], (name, "plain", changed)
-    assert ref, name
-    for k, v in ref.items():  # 4. the specified outputs are not trivial
-        if k not in trivial_ok:
-            assert v.numel() > 0 and _nontrivial(v) > 0, f"{name}: output {k} {tuple(v.shape)} is empty or all 0 / -1"
-    for mode in ("0x00", "0xFF"):
-        got, damage, changed, calls_g, _ = _run(name, mode)
-        # 1. no store outside an output or a workspace
-        assert damage == [], f"{name} [{mode}]: " + "; ".join(str(d) for d in damage)
-        # 3. inputs are const
-        assert changed == [], f"{name} [{mode}]: inputs written: {changed}"
-        # 2. no result depends on what its buffer held before
-        assert set(got) == set(ref), (name, mode, set(got) ^ set(ref))
-        for k, want in ref.items():
-            have = got[k]
-            assert have.shape == want.shape and have.dtype == want.dtype, (name, mode, k, have.shape, want.shape)
-            tols = next((t for (scn, key), t in TOLERANT.items() if scn == name and k.endswith(key)), None)
-            if tols is not None:
-                tol = tols[want.dtype]  # (a dtype without a bound of its own is an error, not a default)
-                err = float((have.double() - want.double()).abs().max())
-                bound = tol * max(float(want.double().abs().max()), 1.0)
-                assert bool(torch.isfinite(have).all()) and err <= bound, f"{name} [{mode}]: {k}: {err} > {bound}"
-                continue
-            same = torch.equal(_bits(have), _bits(want))
-            if not same:
-                diff = (_bits(have) != _bits(want)).nonzero().reshape(-1)
-                first = int(diff[0]) // have.element_size()
-                pytest.fail(f"{name} [{mode}]: output {k} {tuple(have.shape)} {have.dtype} depends on the previous contents "
-                            f"of memory: {diff.numel()} bytes differ from the plain run, first at element {first} "
-                            f"(plain {want.reshape(-1)[first].item()!r}, guarded {have.reshape(-1)[first].item()!r})")
-        assert set(calls_g) == set(calls), (name, mode, set(calls_g) ^ set(calls))
-    for sym, n in calls_g.items():
-        _LEDGER[sym] = _LEDGER.get(sym, 0) + n
-    _RAN.add(name)
+    P.check_scenario(name)
 
 
 # host-only queries: they launch nothing
@@ -1361,14 +1289,6 @@ def test_every_launching_entry_point_is_exercised():
     their plain form under the launch ledger, so the assertion never depends on test selection."""
     from paddle3d_amd import _lib
 
-    for name in SCENARIOS:
-        if name not in _RAN:
-            _, _, _, calls, _ = _run(name, "plain")
-            for sym, n in calls.items():
-                _LEDGER[sym] = _LEDGER.get(sym, 0) + n
-    launching = [s for s in _lib.SYMBOLS if not _host_only(s)]
+    launching = [s for s in _lib.symbols("test_memory_safety_gpu") if not _host_only(s)]
     assert len(NOT_REQUIRED) <= 2 and NOT_REQUIRED <= set(launching)
-    missing = [s for s in launching if s not in NOT_REQUIRED and not _LEDGER.get(s)]
-    assert not missing, (f"{len(missing)} of the {len(launching)} kernel-launching entry points of _lib.SYMBOLS are reached by "
-                         f"no memory-safety scenario: {missing}.  This is intended to fail for a symbol newly added to "
-                         f"_SIGNATURES: add a scenario to tests/test_memory_safety_gpu.py that calls it.")
+    P.check_complete([s for s in launching if s not in NOT_REQUIRED])

@@ -1,12 +1,11 @@
-"""The RoI head's entry points (paddle3d_amd._lib.SYMBOLS_ROI) under guarded allocations: the protocol of
-tests/test_memory_safety_gpu.py.  Each scenario builds seeded inputs and returns `(inputs, call)`; it runs plain,
+"""The RoI head's entry points (the rows of paddle3d_amd._lib.ENTRY_POINTS that name this module) under guarded
+allocations: tests/guarded.py's Protocol.  Each scenario builds seeded inputs and returns `(inputs, call)`; it runs plain,
 guarded with fill 0x00 and guarded with fill 0xFF (tests/guarded.py), and the test asserts: no guard band damaged (no
 store outside an output or a workspace), every input bit-equal to its clone, every specified output bit-equal across
 the three runs (nothing depends on what a buffer held before) and not trivial.  The head scenario constructs the
 module inside the run, so its tensors are allocated under the guard too.
 
-The last test asserts that the scenarios reach every kernel-launching name of SYMBOLS_ROI."""
-import contextlib
+The last test asserts that the scenarios reach every kernel-launching one of them."""
 import os
 import sys
 
@@ -17,7 +16,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(HERE, "golden"))
-from guarded import guarded, launch_ledger  # noqa: E402
+from guarded import Protocol  # noqa: E402
 
 import make_roi_head_golden as mk  # noqa: E402
 
@@ -25,14 +24,8 @@ pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda", 0)
 F32 = np.float32
 
-SCENARIOS = {}
-_LEDGER = {}
-_RAN = set()
-
-
-def scenario(fn):
-    SCENARIOS[fn.__name__] = fn
-    return fn
+P = Protocol("test_memory_safety_roi_gpu", "memory-safety-roi", DEV)
+scenario = P.scenario
 
 
 def _t(a):
@@ -137,72 +130,14 @@ def head_forward():
     return inputs, call
 
 
-def _host(v):
-    return v.detach().contiguous().cpu()
-
-
-def _bits(t):
-    return t.reshape(-1).view(torch.uint8)
-
-
-def _nontrivial(t):
-    x = t.reshape(-1)
-    x = x[~torch.isnan(x)].double() if x.dtype.is_floating_point else x.long()
-    return int(((x != 0) & (x != -1)).sum())
-
-
-def _run(name, mode):
-    from paddle3d_amd import _lib
-
-    print(f"[memory-safety-roi] {name}: {mode}", flush=True)
-    ctx = contextlib.nullcontext(None) if mode == "plain" else guarded(int(mode, 16), DEV)
-    with ctx as g, launch_ledger(_lib.lib(), _lib.SYMBOLS_ROI) as calls:
-        inputs, call = SCENARIOS[name]()
-        before = {k: v.clone() for k, v in inputs.items()}
-        outs = call()
-        torch.cuda.synchronize()
-        damage = g.check() if g is not None else []
-        host = {k: _host(v) for k, v in outs.items()}
-        changed = [k for k, v in inputs.items() if not torch.equal(_bits(_host(v)), _bits(_host(before[k])))]
-        if g is not None:
-            assert len(g.blocks) > 0 and all(buf.data_ptr() % 512 == 0 for buf, _, _, _ in g.blocks)
-    return host, damage, changed, {k: v for k, v in calls.items() if v}
-
-
-@pytest.mark.parametrize("name", list(SCENARIOS))
+@pytest.mark.parametrize("name", list(P.scenarios))
 def test_scenario(name):
-    ref, damage, changed, calls = _run(name, "plain")
-    assert damage == [] and changed == [] and ref, (name, "plain", changed)
-    for k, v in ref.items():
-        assert v.numel() > 0 and _nontrivial(v) > 0, f"{name}: output {k} {tuple(v.shape)} is empty or all 0 / -1"
-    for mode in ("0x00", "0xFF"):
-        got, damage, changed, calls_g = _run(name, mode)
-        assert damage == [], f"{name} [{mode}]: " + "; ".join(str(d) for d in damage)
-        assert changed == [], f"{name} [{mode}]: inputs written: {changed}"
-        assert set(got) == set(ref), (name, mode, set(got) ^ set(ref))
-        for k, want in ref.items():
-            have = got[k]
-            assert have.shape == want.shape and have.dtype == want.dtype, (name, mode, k)
-            if not torch.equal(_bits(have), _bits(want)):
-                diff = (_bits(have) != _bits(want)).nonzero().reshape(-1)
-                first = int(diff[0]) // have.element_size()
-                pytest.fail(f"{name} [{mode}]: output {k} {tuple(have.shape)} depends on the previous contents of "
-                            f"memory: {diff.numel()} bytes differ, first at element {first} "
-                            f"(plain {want.reshape(-1)[first].item()!r}, guarded {have.reshape(-1)[first].item()!r})")
-        assert set(calls_g) == set(calls), (name, mode, set(calls_g) ^ set(calls))
-    for sym, n in calls_g.items():
-        _LEDGER[sym] = _LEDGER.get(sym, 0) + n
-    _RAN.add(name)
+    P.check_scenario(name)
 
 
 def test_every_launching_entry_point_is_exercised():
     """Runs last; scenarios that did not run in this process are run here in their plain form."""
     from paddle3d_amd import _lib
 
-    for name in SCENARIOS:
-        if name not in _RAN:
-            for sym, n in _run(name, "plain")[3].items():
-                _LEDGER[sym] = _LEDGER.get(sym, 0) + n
-    launching = [s for s in _lib.SYMBOLS_ROI if not s.endswith("_workspace")]
-    missing = [s for s in launching if not _LEDGER.get(s)]
-    assert len(launching) == 4 and not missing, f"entry points of SYMBOLS_ROI reached by no scenario: {missing}"
+    launching = [s for s in _lib.symbols("test_memory_safety_roi_gpu") if not s.endswith("_workspace")]
+    P.check_complete(launching, 4)

@@ -3,9 +3,9 @@ csrc/pillar_conv_span.hip) against the three-step form it replaces where its til
 rulebook -> bf16x3 gather-GEMM -> rows to NCHW): the same bytes on every occupancy that takes another path through the
 kernel, the fp64 statement of the layer within the three-step form's own bound
 (tests/test_conv_gpu.py::test_scatter_conv_as_sparse_convolution), the shapes it refuses, SecondBackbone's dispatch.  The
-entry point has its own symbol table (paddle3d_amd._lib.SYMBOLS_SPAN): its scenario under guarded allocations
-(tests/guarded.py, the protocol of tests/test_memory_safety_gpu.py) and the completeness assertion over that table are at
-the end of this file.
+entry point's row in paddle3d_amd._lib.ENTRY_POINTS names this module: its scenario under guarded allocations
+(tests/guarded.py: Protocol) and the completeness assertion over the rows that name this module are at the end of this
+file.
 
 Shapes: 2 frames, input 16 x 512 and 32 x 1024 = one and two 256-cell spans per output row, whose first and last rows and
 columns see the padding; 64 input channels, 64 and 128 output channels (one and two workgroups per span)."""
@@ -16,7 +16,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from guarded import guarded, launch_ledger  # noqa: E402
+from guarded import Protocol, launch_ledger  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -217,12 +217,13 @@ def test_second_backbone_takes_the_span_form_where_it_fits():
     bb.span_first = True
 
 
-_REACHED = {}
+P = Protocol("test_pillar_conv_span_gpu", "pillar-conv-span", "cuda")
 
 
-def _guarded_scenario():
-    """Seeded inputs (made outside the guard) and calls whose outputs -- and the cached weight pieces -- are allocated
-    inside it (torch.empty: stale bytes under the guard): both channel widths, two spans per row."""
+@P.scenario
+def span_form():
+    """Seeded inputs (computed once per case, see _inputs) and calls whose outputs -- and the cached weight pieces -- are
+    allocated under the guard (torch.empty: stale bytes there): both channel widths, two spans per row."""
     from paddle3d_amd.ops import conv
 
     sc64, w64, b64, _ = _inputs("random11", 32, 1024, 64)
@@ -239,43 +240,11 @@ def _guarded_scenario():
 
 
 def test_span_form_under_guarded_allocations():
-    from paddle3d_amd import _lib
-
-    inputs, call = _guarded_scenario()
-    clones = {k: v.clone() for k, v in inputs.items()}
-    runs = {}
-    for mode, fill in (("plain", None), ("fill00", 0x00), ("fillff", 0xFF)):
-        with launch_ledger(_lib.lib(), _lib.SYMBOLS_SPAN) as calls:
-            if fill is None:
-                outs = call()
-                torch.cuda.synchronize()
-                damage = []
-            else:
-                with guarded(fill) as g:
-                    outs = call()
-                    torch.cuda.synchronize()
-                    damage = g.check()
-        assert not damage, (mode, [str(d) for d in damage])
-        for k, v in inputs.items():
-            assert torch.equal(_bits(v), _bits(clones[k])), (mode, k, "an input changed")
-        runs[mode] = {k: v.cpu() for k, v in outs.items()}
-        for sym, c in calls.items():
-            _REACHED[sym] = _REACHED.get(sym, 0) + c
-    for k, want in runs["plain"].items():
-        assert bool(want.any()), k  # not trivial
-        for mode in ("fill00", "fillff"):  # every output element written: stale 0x00 / 0xFF bytes would differ
-            assert torch.equal(runs[mode][k].view(torch.uint8), want.view(torch.uint8)), (mode, k, "depends on the previous contents of memory")
+    P.check_scenario("span_form")
 
 
 def test_every_entry_point_of_symbols_span_is_exercised():
     """Runs last; runs the scenario itself when it was not selected."""
     from paddle3d_amd import _lib
 
-    if not _REACHED:
-        _, call = _guarded_scenario()
-        with launch_ledger(_lib.lib(), _lib.SYMBOLS_SPAN) as calls:
-            call()
-            torch.cuda.synchronize()
-        _REACHED.update(calls)
-    missing = [s for s in _lib.SYMBOLS_SPAN if not _REACHED.get(s)]
-    assert not missing, missing
+    P.check_complete(_lib.symbols("test_pillar_conv_span_gpu"), 1)

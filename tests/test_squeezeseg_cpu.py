@@ -3,14 +3,13 @@ by make_squeezeseg_golden.py): the NumPy restatement of pd3_sac_isk_forward (tes
 modules of paddle3d_amd.squeezesegv3 with fused=False (the torch composition, also what a refused shape runs) within the
 stored bounds; the modules' state-dict keys against the reference's; the restated range projection against the
 reference's pixels, range image and proj_idx exactly, and against a direct transcription of the reader's scatter; the
-packers' round trip, the folded BatchNorm against the unfolded one, `sac_isk_supported`'s borders, SYMBOLS_SQSEG against
-the header and the maker's conditions on the committed file.
+packers' round trip, the folded BatchNorm against the unfolded one, `sac_isk_supported`'s borders
+and the maker's conditions on the committed file.
 
 Bounds: the ones the maker stored, 4 x the largest error of the reference's own fp32 run against its fp64 run (one fp32
 ulp of the largest output as a floor).  Predictions, labels, pixels and proj_idx are compared exactly: the maker keeps
 every logit gap and pixel coordinate further from a decision than those bounds."""
 import os
-import re
 import sys
 
 import numpy as np
@@ -18,7 +17,6 @@ import pytest
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 sys.path.insert(0, os.path.join(HERE, "golden"))
 sys.path.insert(0, HERE)
 import make_squeezeseg_golden as mk  # noqa: E402
@@ -102,18 +100,6 @@ def test_supported_borders():
     assert not ops.sac_isk_supported(32, 0, 5) and not ops.sac_isk_supported(32, 5, 0)
     assert ops.sac_isk_supported(32, 1, 16 * (2 ** 30 - 1)) and not ops.sac_isk_supported(32, 1, 16 * (2 ** 30 - 1) + 1)
     assert ops.MAX_CHANNELS == 256
-
-
-def test_symbol_table_against_the_header():
-    from paddle3d_amd import _lib
-
-    assert _lib.SYMBOLS_SQSEG == ("pd3_sac_isk_forward", "pd3_range_project")
-    header = open(os.path.join(ROOT, "include", "paddle3d_amd.h")).read()
-    for name, (_, args) in _lib._SIGNATURES_SQSEG.items():
-        proto = re.search(r"\bint " + name + r"\(([^;]*)\);", header)
-        assert proto, name
-        assert len(proto.group(1).split(",")) == len(args), name
-    assert not set(_lib.SYMBOLS_SQSEG) & set(_lib.SYMBOLS)
 
 
 def test_folded_batch_norm_equals_the_unfolded_one():

@@ -229,7 +229,7 @@ def test_refusals_and_errors():
     for C in (8, 24, 272):
         xyz, feat = (_t(a) for a in cpu.block_inputs(1, C, 2, 5, 1))
         dummy = torch.zeros(16, device=DEV)
-        with launch_ledger(lib, _lib.SYMBOLS_SQSEG) as n:
+        with launch_ledger(lib, _lib.symbols("test_memory_safety_squeezeseg_gpu")) as n:
             assert ops.sac_isk_forward(xyz, feat, *([dummy] * 6)) is None
         assert not any(n.values())
         out = torch.full_like(feat, 7.0)
@@ -277,7 +277,7 @@ def test_ops_make_no_host_sync_and_launch_once():
     torch.cuda.synchronize()
     torch.cuda.set_sync_debug_mode("error")
     try:
-        with launch_ledger(_lib.lib(), _lib.SYMBOLS_SQSEG) as n:
+        with launch_ledger(_lib.lib(), _lib.symbols("test_memory_safety_squeezeseg_gpu")) as n:
             y = ops.sac_isk_forward(xyz, feat, *dp)
             image = ops.range_project(pts, off, 8, 64)[0]
     finally:

@@ -81,7 +81,7 @@ def measure(fns, iters, repeats):
 def ledger(fn):
     from guarded import launch_ledger
 
-    symbols = _lib.SYMBOLS + _lib.SYMBOLS_ANCHOR3D
+    symbols = _lib.symbols("test_memory_safety_gpu") + _lib.symbols("test_memory_safety_anchor3d_gpu")
     with launch_ledger(_lib.lib(), symbols) as calls:
         fn()
     return {k: v for k, v in calls.items() if v}
