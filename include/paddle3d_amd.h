@@ -44,6 +44,23 @@ const char *pd3_target_arch(void);
 int pd3_selfcheck_lds_atomic_order(const uint32_t *addr, uint32_t *old, int blocks, int waves_per_block, int rounds,
                                    int table, void *stream);
 
+/* Self-check of the block top-K selection the post-processing kernels share (csrc/block_topk.hpp: radix cut,
+ * compaction, bitonic sort) on raw keys.  One 1024-thread workgroup per set selects the K smallest counted keys of
+ * keys [sets][n] uint32 in ascending (key, index) order -- what a stable sort gives -- with the header's own functions.
+ *   counted   a key below 2^key_bits (1 <= key_bits <= 30) that is not `leave_out` (a key value the caller's visit
+ *             skips, the SSD head's convention; < 0: none).  A key not counted must sort after every key taken.
+ *   form      0: keys read from global memory, block_topk_compact; 1: keys staged into LDS, block_topk_compact_chunks
+ *             (n <= 16384), as CenterPoint's selection does
+ *   skip_cut  nonzero: no radix cut, the callers' take-all TopkCut{0xFFFFFFFF, 0} (every key below 0xFFFFFFFF)
+ *   idx, key  [sets][K] uint32: low and high word of the sorted list (index, key); 0xFFFFFFFF past the taken entries
+ *   cut       [sets][2] uint32: kc, r as block_topk_cut returned them
+ * A set that breaks the selection's precondition (skip_cut == 0: more than K keys counted; always: no more than K
+ * entries taken) is not selected from: all of its idx, key and cut words are 0xFFFFFFFF.
+ * PD3_EINVAL for a NULL pointer, K outside [1, 1024], key_bits outside [1, 30], n < 1, sets < 0, a form other than
+ * 0 / 1, form 1 with n > 16384; nothing is launched for sets == 0.  No reference counterpart. */
+int pd3_selfcheck_block_topk(const uint32_t *keys, int sets, int n, int K, int key_bits, int form, int64_t leave_out,
+                             int skip_cut, uint32_t *idx, uint32_t *key, uint32_t *cut, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * hard_voxelize -- replaces PD_BUILD_OP(hard_voxelize), paddle3d/ops/voxel/voxelize_op.cc:183-191
  * (kernel fn hard_voxelize :149-166; CPU semantics hard_voxelize_cpu_kernel :19-82, which this

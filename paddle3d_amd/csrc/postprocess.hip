@@ -303,6 +303,8 @@ __global__ __launch_bounds__(kTopkThreads) void cp_topk_kernel(CpHeads h, CpCfg 
   const int K = min(count, cap);
   if (K <= 0) return;
   // ---- selection (block_topk.hpp); at a positive threshold kKeyOut lies above key_bits and is not counted ----------
+  // At a threshold <= 0 key_bits is 30 and kKeyOut (< 2^30) IS counted, in bin 1023 of digit 1: real keys end at
+  // bits(1.0f) in bin 1016, and rank K <= count lies among them, so kc <= 1017 << 20 (bin 1016 whole) < kKeyOut.
   // entry = key : cell : position in this list -- the order of (key, cell) with the way back to the position
   const TopkCut cut = count > K ? block_topk_cut(K, key_bits, hist, scr,
                                                  [&](auto f) {

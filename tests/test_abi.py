@@ -42,7 +42,7 @@ SCALARS = {"float": C.c_float, "double": C.c_double, "int": C.c_int, "int64_t": 
            "size_t": C.c_size_t}
 # the table's blocks: the names whose guarded scenarios live in tests/<module>.py (a count for the large first one)
 BLOCKS = {
-    "test_memory_safety_gpu": 102,
+    "test_memory_safety_gpu": 103,
     "test_memory_safety_roi_gpu": {"pd3_voxel_pool", "pd3_roi_grid_points", "pd3_rcnn_decode_boxes",
                                    "pd3_class_agnostic_nms_workspace", "pd3_class_agnostic_nms"},
     "test_grouped_counts_gpu": {"pd3_grouped_conv3x3_small_counts_slice"},
@@ -92,7 +92,7 @@ def test_entry_points_match_the_header(built):
 def test_entry_points_name_the_module_of_their_scenarios():
     from paddle3d_amd import _lib
 
-    assert len(_lib.symbols()) == len(_lib.ENTRY_POINTS) == 131
+    assert len(_lib.symbols()) == len(_lib.ENTRY_POINTS) == 132
     assert list(dict.fromkeys(row[2] for row in _lib.ENTRY_POINTS.values())) == list(BLOCKS)
     for module, want in BLOCKS.items():
         assert os.path.isfile(os.path.join(ROOT, "tests", module + ".py")), module

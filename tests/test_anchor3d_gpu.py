@@ -211,6 +211,59 @@ def test_candidate_counts_at_the_nms_tile(n):
         same_results(from_maps((cls, reg, dirs), anchors, cfg), want, f"{n} candidates, spread {spread}")
 
 
+import topk_lattice as TL  # noqa: E402
+
+
+def _far_apart(rng, H, W, A):
+    anchors = sweep_anchors(rng, H, W, A, TL.A3D_CS)
+    anchors[:, :2] *= F32(10.0)   # no two boxes overlap: the NMS keeps every candidate
+    return anchors
+
+
+@pytest.mark.parametrize("grid", list(TL.A3D_GRIDS))
+@pytest.mark.parametrize("nms_pre", TL.A3D_NMS_PRE)
+def test_selection_lattice_nms_pre(grid, nms_pre):
+    """a3d_topk_kernel at nms_pre 63 / 64 / 65 / 129 / 1024 with N & 3 both ways (the float4 and the scalar walk): the
+    cut lies inside ten equal scores, five taken, the other five in the next wave of block_topk_compact
+    (tests/test_topk_lattice_cpu.py::test_anchor3d_call_site_labels).  Bit for bit against the restatement."""
+    H, W, A = TL.A3D_GRIDS[grid]
+    x, cluster = TL.a3d_select_case(grid, nms_pre)
+    rng = np.random.default_rng(nms_pre)
+    anchors = _far_apart(rng, H, W, A)
+    cls, reg, dirs = TL.a3d_maps(H, W, A, x, nms_pre)
+    cfg = dict(nms_pre=nms_pre, max_num=500, score_thr=0.05, nms_thr=0.2, dir_offset=0.0, dir_limit_offset=1.0,
+               num_classes=TL.A3D_NC)
+    trace = {}
+    an.frame_bboxes(cls[0], reg[0], dirs[0], anchors, cfg, trace=trace)
+    sel = trace["sel"]
+    assert len(sel) == nms_pre and np.array_equal(np.intersect1d(sel, cluster), cluster[:5])
+    want = an.get_bboxes(cls, reg, dirs, anchors, cfg)
+    assert 0 < want[3][0] <= min(nms_pre, 500)      # (the two rotations of a pixel overlap: the NMS drops a few)
+    same_results(from_maps((cls, reg, dirs), anchors, cfg), want, f"{grid} nms_pre {nms_pre}")
+
+
+@pytest.mark.parametrize("n", TL.A3D_SET_SIZES)
+def test_selection_lattice_class_sets_and_max_num(n):
+    """A class set of exactly 64, 65 and 129 candidates (a3d_class_sets_kernel's block_topk_sort alone: n2 = 64, 128 and
+    256, the last with block barriers inside the network), tied scores inside; then two classes whose kept candidates
+    number max_num + 1 (a3d_output_kernel's cut over the concatenated keys takes all but one)."""
+    for total_cut in (False, True):
+        (H, W, A), x = TL.a3d_set_case(n, total_cut)
+        rng = np.random.default_rng(n)
+        anchors = _far_apart(rng, H, W, A)
+        cls, reg, dirs = TL.a3d_maps(H, W, A, x, n)
+        total = n + (n // 2 if total_cut else 0)
+        cfg = dict(nms_pre=1000, max_num=total - 1 if total_cut else 500, score_thr=0.3, nms_thr=0.2, dir_offset=0.0,
+                   dir_limit_offset=1.0, num_classes=TL.A3D_NC)
+        trace = {}
+        an.frame_bboxes(cls[0], reg[0], dirs[0], anchors, cfg, trace=trace)
+        sizes = [(c, len(cand), len(keep)) for c, cand, keep in trace["sets"]]
+        assert sizes == ([(0, n, n), (1, n // 2, n // 2)] if total_cut else [(0, n, n)]) and trace["total"] == total
+        want = an.get_bboxes(cls, reg, dirs, anchors, cfg)
+        assert want[3][0] == (total - 1 if total_cut else n)
+        same_results(from_maps((cls, reg, dirs), anchors, cfg), want, f"class set of {n}, total cut {total_cut}")
+
+
 def test_hostile_data():
     rng = np.random.default_rng(77)
     H, W, A, nc, cs = 6, 9, 6, 3, 9

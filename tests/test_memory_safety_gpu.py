@@ -1268,6 +1268,37 @@ def selfcheck_lds_atomic_order():
     return inputs, call
 
 
+@scenario
+def selfcheck_block_topk():
+    """The block top-K selection's probe: two sets, keys from global memory (form 0) and staged into LDS (form 1), with
+    a left-out value and keys above 2^key_bits.  idx / key [sets][K] and cut [sets][2], all whole."""
+    rng = np.random.default_rng(23)
+    n, K, key_bits, leave_out = 4097, 129, 21, (1 << 21) - 1
+    keys = rng.integers(0, 1 << 21, (2, n)).astype(np.uint32)
+    keys[0, ::5] = leave_out
+    keys[1, ::7] = 0xFFFFFFFF
+    keys[1, 100:400] = 0                    # 300 keys tie for the first K = 129 places: the cut lies among them
+    inputs = dict(keys=_t(keys.view(np.int32)))
+
+    def call():
+        lib, check, ptr, stream = _lib()
+        outs = {}
+        for form in (0, 1):
+            idx = torch.empty((2, K), dtype=torch.int32, device=DEV)
+            key = torch.empty((2, K), dtype=torch.int32, device=DEV)
+            cut = torch.empty((2, 2), dtype=torch.int32, device=DEV)
+            check(lib.pd3_selfcheck_block_topk(ptr(inputs["keys"]), 2, n, K, key_bits, form, leave_out, 0, ptr(idx),
+                                               ptr(key), ptr(cut), stream), "selfcheck_block_topk")
+            outs.update({f"idx{form}": idx, f"key{form}": key, f"cut{form}": cut})
+        assert torch.equal(outs["idx0"], outs["idx1"])
+        for form in (0, 1):                 # neither set refused (a refused set's words are all 0xFFFFFFFF)
+            assert (outs[f"cut{form}"] != -1).any(dim=1).all() and (outs[f"idx{form}"] != -1).all()
+        assert outs["cut0"][1].tolist() == [0, K]
+        return outs
+
+    return inputs, call
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", list(P.scenarios))
 def test_scenario(name):

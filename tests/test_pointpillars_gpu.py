@@ -231,6 +231,50 @@ def test_ssd_postprocess_variants_and_edges(oracle):
     assert [d["scores"].numel() for d in head0.post_process(m, gen, _cuda(co))] == [0, 0]  # order[:0]: nothing to keep
 
 
+def _ssd_lattice():
+    sys.path.insert(0, HERE)
+    import topk_lattice
+
+    return topk_lattice
+
+
+@pytest.mark.parametrize("grid,tname,pre_kind", _ssd_lattice().SSD_CASES)
+def test_ssd_postprocess_selection_lattice(oracle, grid, tname, pre_kind):
+    """ssd_topk_kernel on the cases of tests/topk_lattice.py (labels: test_topk_lattice_cpu.py::
+    test_ssd_call_site_labels).  A score threshold <= 0 keeps every anchor the pillar mask keeps: key_bits is 30, and
+    the masked anchors' key (kSsdKeyOut, most of the frame) lies BELOW 2^key_bits -- the kernel leaves it out in its
+    visit; a threshold of 0.05 derives a narrower width.  Small grids with an anchor count that is a multiple of four
+    (the uint4 walk) and one that is not (the scalar walk); a cluster of ten equal logits at the cut, five taken, the
+    other five in the next wave of block_topk_compact; the cap at one frame's count - 1 (count == pre + 1).  Against the
+    full sort (same bytes) and the oracle (the tolerances of the tests above)."""
+    from paddle3d_amd.pointpillars import AnchorGenerator, SSDHead
+
+    L = _ssd_lattice()
+    args, co, masks, ncls = L.ssd_setup(grid)
+    cls, pre, thr, clusters = L.ssd_case(grid, tname, pre_kind)
+    gen = AnchorGenerator(*args).cuda()
+    fh, fw = gen.feature_map_size
+    apl, a = gen.num_anchors_per_loc, gen.anchors.shape[0]
+    assert a == masks.shape[1] and ((a & 3) == 0) == (grid == "n&3==0")
+    rng = np.random.default_rng(9)
+    box = rng.normal(0, 0.35, (2, a, 7)).astype(np.float32)
+    dirp = rng.normal(0, 1, (2, a, 2)).astype(np.float32)
+    m = _cuda(_map_from_preds(cls, box, dirp, fh, fw, apl))
+    an = gen.anchors.cpu().numpy()
+    head = SSDHead(ncls, 32, apl, nms_score_threshold=thr, nms_pre_max_size=pre, nms_post_max_size=200,
+                   nms_iou_threshold=0.3, prediction_center_limit_range=None).cuda().eval()
+    dets = head.post_process(m, gen, _cuda(co))
+    for d, e in zip(dets, head.post_process(m, gen, _cuda(co), full_sort=True)):  # both selections, same bytes
+        for k in ("box3d_lidar", "scores", "label_preds"):
+            assert torch.equal(d[k], e[k]), k
+    for b in range(2):
+        rb, rs, rl = oracle.ssd_post_process_frame_numpy(box[b], cls[b], dirp[b], an, masks[b], thr, None, pre, 200, 0.3)
+        assert rs.shape[0] > 3
+        np.testing.assert_array_equal(dets[b]["label_preds"].cpu().numpy(), rl)
+        np.testing.assert_allclose(dets[b]["scores"].cpu().numpy(), rs, rtol=0, atol=3e-7)
+        np.testing.assert_allclose(dets[b]["box3d_lidar"].cpu().numpy(), rb, rtol=1e-6, atol=4e-6)
+
+
 def _randomise_bn(model, seed=0):
     g = torch.Generator().manual_seed(seed)
     with torch.no_grad():
