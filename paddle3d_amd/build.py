@@ -46,7 +46,9 @@ def _stale(target, deps):
 # per-file additions.  The two F(4x4, 3x3) ping-pong kernels are compiled without the SLP vectoriser: in their output step
 # A^T M A (and in the pair transform) every v_pk_add_f32 / v_pk_fma_f32 it forms is fed by two to four v_mov_b32 that gather
 # its operands, which costs more issue slots than the scalar instructions it replaces (the precomputed-V kernel: 672
-# v_mov_b32 with it, 2 without).  The packed ops compute what the scalar ones do: the bytes out do not change.
+# v_mov_b32 with it, 2 without).  The packed ops compute what the scalar ones do: the bytes out do not change.  The packed
+# instructions the ping-pong kernel does issue are written by hand on register pairs that are read from LDS as pairs (w4_in2
+# in conv_winograd43.hpp): a v_pk_* with its operands in place costs one issue slot (tools/hwcheck/lane_swap_pk_rates.hip).
 EXTRA_FLAGS = {"conv_winograd43_pp.hip": ["-fno-slp-vectorize"], "conv_winograd43_ppv.hip": ["-fno-slp-vectorize"]}
 
 

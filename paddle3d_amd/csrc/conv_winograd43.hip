@@ -79,9 +79,10 @@ __global__ __launch_bounds__(128 * CB, CB == 2 ? 2 : 1) void conv3x3_winograd43_
 #pragma unroll
   for (int i = 0; i < UPT; ++i) uofs[i] = min(max((int)threadIdx.x - UT0, 0) + i * 256, UN4 - 1);
   const bool transforms = threadIdx.x < 256;     // wave-uniform
-  // transform assignment: thread pair (2p, 2p+1) owns patch p = (ci, tile); half hf = columns / rows 3hf..3hf+2
-  const int pidx = threadIdx.x >> 1, hf = threadIdx.x & 1;
-  const int pci = pidx >> 5, ptile = pidx & 31;
+  // transform assignment: lanes l and l ^ 16 of wave ci (0..3) own patch (ci, tile); half hf = columns / rows 3hf..3hf+2.
+  // A 32-lane half of the wave covers one tile row x 16 tiles x both halves (conv_winograd43_pp.hip has the LDS banks)
+  const int hf = (lane >> 4) & 1;
+  const int pci = wave & 3, ptile = (lane >> 5) * 16 + (lane & 15);
   const int rsrc = pci * kW4RawPl + (4 * (ptile >> 4)) * kW4RawW + 4 * (ptile & 15) + 3 + 3 * hf;
   const int vdst = (((ptile >> 4) * kW4Ci + pci) * kW4TC + (ptile & 15)) * kW4Cs + 18 * hf;
   // MFMA operand bases
@@ -122,12 +123,14 @@ __global__ __launch_bounds__(128 * CB, CB == 2 ? 2 : 1) void conv3x3_winograd43_
   // V = B^T d B of the pair's patch, from Raw to Vnext
   auto transform = [&]() {
     if (CB == 2 || transforms) {
-      float rv[3][6];
+      w4_f32x2 r01[6];
+      float r2[6];
 #pragma unroll
-      for (int b = 0; b < 3; ++b)
-#pragma unroll
-        for (int r = 0; r < 6; ++r) rv[b][r] = Raw[rsrc + b + r * kW4RawW];
-      w4_pair_transform(rv, hf, Vnext + vdst);
+      for (int r = 0; r < 6; ++r) {
+        r01[r] = (w4_f32x2){Raw[rsrc + r * kW4RawW], Raw[rsrc + r * kW4RawW + 1]};
+        r2[r] = Raw[rsrc + r * kW4RawW + 2];
+      }
+      w4_pair_transform(r01, r2, Vnext + vdst);
     }
   };
   // one trip: 9 groups of 4 components

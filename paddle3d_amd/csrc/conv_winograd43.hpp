@@ -47,44 +47,71 @@ __device__ __forceinline__ void w4_out(const float m0, const float m1, const flo
   s[3] = __builtin_fmaf(8.f, u, q) + m5;
 }
 
-__device__ __forceinline__ float w4_swap_pair(float v) {  // value of the neighbouring lane (lane ^ 1)
-  return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, true));
+// w4_in on both halves of a register pair at once (v_pk_add_f32 / v_pk_fma_f32: one issue slot each on gfx950 when the
+// pair lies adjacent as it is, tools/hwcheck/lane_swap_pk_rates.hip): every half sees w4_in's operations, in their order
+__device__ __forceinline__ w4_f32x2 w4_fma2(const float k, const w4_f32x2 x, const w4_f32x2 y) {
+  return __builtin_elementwise_fma((w4_f32x2){k, k}, x, y);
+}
+__device__ __forceinline__ void w4_in2(const w4_f32x2 d0, const w4_f32x2 d1, const w4_f32x2 d2, const w4_f32x2 d3,
+                                       const w4_f32x2 d4, const w4_f32x2 d5, w4_f32x2 (&t)[6]) {
+  const w4_f32x2 a = w4_fma2(-4.f, d2, d4), b = w4_fma2(-4.f, d1, d3);
+  const w4_f32x2 c = d4 - d2, e = d3 - d1;
+  t[0] = w4_fma2(4.f, d0, w4_fma2(-5.f, d2, d4));
+  t[1] = a + b;
+  t[2] = a - b;
+  t[3] = w4_fma2(2.f, e, c);
+  t[4] = w4_fma2(-2.f, e, c);
+  t[5] = w4_fma2(4.f, d1, w4_fma2(-5.f, d3, d5));
+}
+
+// (lo[i], hi[i]) of this lane and of lane ^ 16 -> (own lo, partner's lo) on the lanes of an even row of 16, (partner's hi,
+// own hi) on those of an odd row: ONE v_permlane16_swap_b32 per value (8 cycles of issue, where the two DPP moves and two
+// selects of a lane ^ 1 pairing take 16).  Spelled out, and the nine of a transform as one block: this compiler's
+// __builtin_amdgcn_permlane16_swap hands back its FIRST result for both (measured: lane 0 got (own lo, own lo)), and inside
+// inline assembly the two wait states between a VALU write of an operand and the swap that reads it are ours to keep --
+// one s_nop 1 in front of the block (8 cycles, once) covers whatever wrote the operands last; the swaps themselves touch
+// disjoint registers.
+__device__ __forceinline__ void w4_swap_halves9(float (&lo)[9], float (&hi)[9]) {
+  asm volatile(
+      "s_nop 1\n\t"
+      "v_permlane16_swap_b32 %0, %9\n\t"
+      "v_permlane16_swap_b32 %1, %10\n\t"
+      "v_permlane16_swap_b32 %2, %11\n\t"
+      "v_permlane16_swap_b32 %3, %12\n\t"
+      "v_permlane16_swap_b32 %4, %13\n\t"
+      "v_permlane16_swap_b32 %5, %14\n\t"
+      "v_permlane16_swap_b32 %6, %15\n\t"
+      "v_permlane16_swap_b32 %7, %16\n\t"
+      "v_permlane16_swap_b32 %8, %17"
+      : "+v"(lo[0]), "+v"(lo[1]), "+v"(lo[2]), "+v"(lo[3]), "+v"(lo[4]), "+v"(lo[5]), "+v"(lo[6]), "+v"(lo[7]), "+v"(lo[8]),
+        "+v"(hi[0]), "+v"(hi[1]), "+v"(hi[2]), "+v"(hi[3]), "+v"(hi[4]), "+v"(hi[5]), "+v"(hi[6]), "+v"(hi[7]), "+v"(hi[8]));
 }
 
 // (w4_lds_barrier, the workgroup barrier that orders LDS traffic only: lds_dma.hpp)
 
-// V = B^T d B of a thread pair's patch, from the six rows of this lane's three columns (rv[b][r] = d[r][3 hf + b]) to the
-// lane's 18 components at v.  Row pass on this lane's three columns, halves swapped between the pair, column pass on this
+// V = B^T d B of a thread pair's patch -- lanes l and l ^ 16 of a wave, half hf = (l >> 4) & 1 -- from the six rows of this
+// lane's three columns (r01[r] = d[r][3 hf + 0, 1], r2[r] = d[r][3 hf + 2]) to the lane's 18 components at v.  Row pass on
+// this lane's three columns (columns 0 and 1 as a register pair), halves swapped between the pair, column pass on this
 // lane's three rows; components (row, nu) -> 6 row + nu.
-// (inline, not __forceinline__: forced in before its loops are unrolled, the SLP vectoriser pairs the passes differently --
-// 38 v_pk_fma_f32 where this gives 46 -- and the ping-pong kernel's register allocation moves with it; it is inlined in
-// both its callers either way)
-__device__ inline void w4_pair_transform(const float (&rv)[3][6], const int hf, float* v) {
-  float lo[3][3], hi[3][3];  // (B^T d)[row a or 3 + a][my column b]
-#pragma unroll
-  for (int b = 0; b < 3; ++b) {
-    float t[6];
-    w4_in(rv[b][0], rv[b][1], rv[b][2], rv[b][3], rv[b][4], rv[b][5], t);
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      lo[a][b] = t[a];
-      hi[a][b] = t[3 + a];
-    }
-  }
-  // the even lane runs the column pass for rows 0..2, the odd lane for rows 3..5; what a lane lacks are the other three
-  // columns of its rows, i.e. the partner's lo (even lane) or hi (odd lane): one select with a DPP-swapped operand per
-  // value
+__device__ inline void w4_pair_transform(const w4_f32x2 (&r01)[6], const float (&r2)[6], float* v) {
+  w4_f32x2 t01[6];  // (B^T d)[row][my columns 0, 1]
+  float t2[6];      // (B^T d)[row][my column 2]
+  w4_in2(r01[0], r01[1], r01[2], r01[3], r01[4], r01[5], t01);
+  w4_in(r2[0], r2[1], r2[2], r2[3], r2[4], r2[5], t2);
+  // the hf = 0 lane runs the column pass for rows 0..2, the hf = 1 lane for rows 3..5; what a lane lacks are the other
+  // three columns of its rows, i.e. the partner's rows 0..2 (hf = 0) or 3..5 (hf = 1) of ITS columns: rows a and 3 + a
+  // trade places between the two lanes, one swap per column
+  float f[9], l[9];  // [3 a + b] -> columns 0..2 / 3..5 of row 3 hf + a of B^T d
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    float f[3], l[3];  // columns 0..2 / 3..5 of row 3 hf + a of B^T d
+    f[3 * a] = t01[a][0], f[3 * a + 1] = t01[a][1], f[3 * a + 2] = t2[a];
+    l[3 * a] = t01[3 + a][0], l[3 * a + 1] = t01[3 + a][1], l[3 * a + 2] = t2[3 + a];
+  }
+  w4_swap_halves9(f, l);
 #pragma unroll
-    for (int b = 0; b < 3; ++b) {
-      const float ph = w4_swap_pair(hi[a][b]), pl = w4_swap_pair(lo[a][b]);
-      f[b] = hf ? ph : lo[a][b];
-      l[b] = hf ? hi[a][b] : pl;
-    }
+  for (int a = 0; a < 3; ++a) {
     float o[6];
-    w4_in(f[0], f[1], f[2], l[0], l[1], l[2], o);
+    w4_in(f[3 * a], f[3 * a + 1], f[3 * a + 2], l[3 * a], l[3 * a + 1], l[3 * a + 2], o);
     *reinterpret_cast<w4_f32x2*>(v + a * 6 + 0) = (w4_f32x2){o[0], o[1]};
     *reinterpret_cast<w4_f32x2*>(v + a * 6 + 2) = (w4_f32x2){o[2], o[3]};
     *reinterpret_cast<w4_f32x2*>(v + a * 6 + 4) = (w4_f32x2){o[4], o[5]};

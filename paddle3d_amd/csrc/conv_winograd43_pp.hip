@@ -71,7 +71,6 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winograd43_pp_kernel(const flo
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int lane = lane_id(), wave = __builtin_amdgcn_readfirstlane(wave_id());  // (uniform: scalar slot control)
   const int grp = wave >> 2, cb = wave & 3;  // tile row / 16-channel block of this wave; waves w and w + 4 share a SIMD
-  const int gt = cb * 64 + lane;             // thread inside its group
   float* Us = smem;                                          // [2 trips][4 cb][9][64 lanes][4]: U of the current slot
   float* Raw = smem + kPpUsz + grp * (kPpRawSz + kPpVsz);    // [8 ci][6 rows][72 cols] of this group's tile row
   float* Vs = Raw + kPpRawSz;                      // [8 ci][16 tiles][36]
@@ -98,9 +97,15 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winograd43_pp_kernel(const flo
     const bool ok = gy >= 0 && gy < h && gx >= 0 && gx < w;
     gofs[i] = ok ? (unsigned)(4 * ((2 * cb + cl) * plane + (int64_t)gy * w + gx)) : 0x7ffffff0u;
   }
-  // transform assignment: thread pair (2p, 2p+1) of the group owns patch p = (ci 0..7, tile column 0..15)
-  const int pidx = gt >> 1, hf = gt & 1;
-  const int pci = pidx >> 4, ptile = pidx & 15;
+  // transform assignment: lanes l and l ^ 16 of a wave own one patch (ci 0..7, tile column 0..15) -- rows of 16 lanes are
+  // the halves, which one v_permlane16_swap_b32 per value exchanges (w4_pair_transform).  A 32-lane half of the wave
+  // covers one channel plane x 16 tiles x both halves, the same LDS addresses as with neighbouring lanes paired: the row
+  // reads (two lanes per bank of the 32, as before) and, per 32 lanes, the V stores keep their patterns; an 8-byte store
+  // goes by 16 lanes, which now are 16 tiles of one half -- 36 floats apart, 4 banks: two lanes per bank pair, where the
+  // 18 apart of a tile's two halves gave one (9 stores per slot and wave, about 36 LDS cycles, against the 64 cycles of
+  // issue the nine swaps save; lanes 32 apart as pairs would put both channel planes, 432 apart, into one half)
+  const int hf = (lane >> 4) & 1;
+  const int pci = 2 * cb + (lane >> 5), ptile = lane & 15;
   const int rsrc = pci * kPpRawPl + 4 * ptile + 3 + 3 * hf;
   const int vdst = (pci * kW4TC + ptile) * kW4Cs + 18 * hf;
   const int bbase = pp_bbase(lane);
@@ -128,16 +133,18 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winograd43_pp_kernel(const flo
   // The wave's raw rows of the NEXT transform slot are read into registers at the end of the wave's multiply slot, in front
   // of the barrier: behind it the other group's MFMAs hold the SIMD, and LDS reads issued then return when that stream
   // ends (pingpong_skeleton: more than four reads wait for it) -- 340-450 cycles of every time slot.
-  float rv[3][6];
+  // (columns 0 and 1 of a row as a register pair, for the packed row pass)
+  w4_f32x2 r01[6];
+  float r2[6];
   auto read_rows = [&]() {
+    const float* d = Raw + rsrc;
 #pragma unroll
-    for (int b = 0; b < 3; ++b) {
-      const float* d = Raw + rsrc + b;
-#pragma unroll
-      for (int r = 0; r < 6; ++r) rv[b][r] = d[r * kW4RawW];
+    for (int r = 0; r < 6; ++r) {
+      r01[r] = (w4_f32x2){d[r * kW4RawW], d[r * kW4RawW + 1]};
+      r2[r] = d[r * kW4RawW + 2];
     }
   };
-  // V = B^T d B of this thread pair's patch (w4_pair_transform), from the rows in rv[].  The fetch of the NEXT slot's
+  // V = B^T d B of this thread pair's patch (w4_pair_transform), from the rows in r01[], r2[].  The fetch of the NEXT slot's
   // rows (slot sn) goes out first -- the memory pipe takes it while the SIMD is held -- and has the rest of this slot and
   // the wave's multiply slot to land.
   auto transform = [&](int sn, auto&& after_fetch) {
@@ -145,7 +152,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winograd43_pp_kernel(const flo
     after_fetch();
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_sched_barrier(0);
-    w4_pair_transform(rv, hf, Vs + vdst);
+    w4_pair_transform(r01, r2, Vs + vdst);
   };
   // a multiply slot: 72 MFMAs, one stream over both trips, fed by ds_read_b128 alone; B through a ring of three reads, two
   // groups ahead.  No buffer_load ... lds here: one piece costs an MFMA stream 60-185 cycles of issue (measured: a group
