@@ -31,8 +31,11 @@ def _block(scenarios, rows):
 
 
 def symbols(module=None):
-    """Every entry point's name in table order, or those whose guarded scenarios live in tests/<module>.py."""
-    return tuple(name for name, row in ENTRY_POINTS.items() if module is None or row[2] == module)
+    """Every name of ENTRY_POINTS in table order, or those (of either table) whose guarded scenarios live in
+    tests/<module>.py."""
+    if module is None:
+        return tuple(ENTRY_POINTS)
+    return tuple(name for table in (ENTRY_POINTS, SMOKE_ENTRY_POINTS) for name, row in table.items() if row[2] == module)
 
 
 # the first models' ops: voxelization, pillar encoders, NMS, post-processing, point ops, sparse and dense convolutions
@@ -336,6 +339,17 @@ _block("test_memory_safety_iassd_gpu", {
                          [C.c_void_p] * 2),
 })
 
+# SMOKE's head and post-processing (csrc/smoke.hip), declared in include/paddle3d_amd_smoke.h.  A table of its own beside
+# ENTRY_POINTS (whose size and blocks tests/test_abi.py pins), in the same row format; tests/test_abi_smoke.py holds it to
+# its header, and symbols("test_memory_safety_smoke_gpu") names its rows.
+_SMOKE_CFG = [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]
+SMOKE_ENTRY_POINTS = {name: row + ("test_memory_safety_smoke_gpu",) for name, row in {
+    "pd3_smoke_head_workspace": (C.c_size_t, [C.c_int] * 5),
+    "pd3_smoke_head_forward": (C.c_int, [C.c_void_p] * 2 + [C.c_int64, C.c_int] + [C.c_void_p] * 15 + [C.c_int] * 6 +
+                               _SMOKE_CFG),
+    "pd3_smoke_post_process": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 4 + _SMOKE_CFG),
+}.items()}
+
 
 class Paddle3DAmdError(RuntimeError):
     pass
@@ -348,7 +362,7 @@ def lib() -> C.CDLL:
             f"{LIB_PATH} not found: build it with `python -m paddle3d_amd.build` "
             "(there is no CPU / PyTorch fallback for the HIP ops)")
     handle = C.CDLL(LIB_PATH)
-    for name, (res, args, _) in ENTRY_POINTS.items():
+    for name, (res, args, _) in list(ENTRY_POINTS.items()) + list(SMOKE_ENTRY_POINTS.items()):
         try:
             fn = getattr(handle, name)
         except AttributeError as e:  # pragma: no cover
