@@ -31,12 +31,8 @@ def _block(scenarios, rows):
 
 
 def symbols(module=None):
-    """Every name of ENTRY_POINTS in table order, or those (of any of the three tables) whose guarded scenarios live in
-    tests/<module>.py."""
-    if module is None:
-        return tuple(ENTRY_POINTS)
-    return tuple(name for table in (ENTRY_POINTS, SMOKE_ENTRY_POINTS, DD3D_ENTRY_POINTS) for name, row in table.items()
-                 if row[2] == module)
+    """Every name of ENTRY_POINTS in table order, or those whose guarded scenarios live in tests/<module>.py."""
+    return tuple(name for name, row in ENTRY_POINTS.items() if module is None or row[2] == module)
 
 
 # the first models' ops: voxelization, pillar encoders, NMS, post-processing, point ops, sparse and dense convolutions
@@ -340,26 +336,22 @@ _block("test_memory_safety_iassd_gpu", {
                          [C.c_void_p] * 2),
 })
 
-# SMOKE's head and post-processing (csrc/smoke.hip), declared in include/paddle3d_amd_smoke.h.  A table of its own beside
-# ENTRY_POINTS (whose size and blocks tests/test_abi.py pins), in the same row format; tests/test_abi_smoke.py holds it to
-# its header, and symbols("test_memory_safety_smoke_gpu") names its rows.
+# SMOKE's head and post-processing (csrc/smoke.hip)
 _SMOKE_CFG = [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]
-SMOKE_ENTRY_POINTS = {name: row + ("test_memory_safety_smoke_gpu",) for name, row in {
+_block("test_memory_safety_smoke_gpu", {
     "pd3_smoke_head_workspace": (C.c_size_t, [C.c_int] * 5),
     "pd3_smoke_head_forward": (C.c_int, [C.c_void_p] * 2 + [C.c_int64, C.c_int] + [C.c_void_p] * 15 + [C.c_int] * 6 +
                                _SMOKE_CFG),
     "pd3_smoke_post_process": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 4 + _SMOKE_CFG),
-}.items()}
+})
 
-# DD3D's FCOS heads and post-processing (csrc/dd3d.hip), declared in include/paddle3d_amd_dd3d.h: a third table in the
-# same row format, for the same reason; tests/test_abi_dd3d.py holds it to its header, and
-# symbols("test_memory_safety_dd3d_gpu") names its rows.
+# DD3D's FCOS heads and post-processing (csrc/dd3d.hip)
 _DD3D_CFG = [C.c_int] * 4 + [C.c_float] * 5 + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]  # pre_nms_topk .. stream
-DD3D_ENTRY_POINTS = {name: row + ("test_memory_safety_dd3d_gpu",) for name, row in {
+_block("test_memory_safety_dd3d_gpu", {
     "pd3_dd3d_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]),
     "pd3_dd3d_head_forward": (C.c_int, [C.c_void_p] * 12 + [C.c_int] * 6 + _DD3D_CFG),
     "pd3_dd3d_post_process": (C.c_int, [C.c_void_p] * 11 + [C.c_int] * 4 + _DD3D_CFG),
-}.items()}
+})
 
 
 class Paddle3DAmdError(RuntimeError):
@@ -373,8 +365,7 @@ def lib() -> C.CDLL:
             f"{LIB_PATH} not found: build it with `python -m paddle3d_amd.build` "
             "(there is no CPU / PyTorch fallback for the HIP ops)")
     handle = C.CDLL(LIB_PATH)
-    for name, (res, args, _) in [row for table in (ENTRY_POINTS, SMOKE_ENTRY_POINTS, DD3D_ENTRY_POINTS)
-                                 for row in table.items()]:
+    for name, (res, args, _) in ENTRY_POINTS.items():
         try:
             fn = getattr(handle, name)
         except AttributeError as e:  # pragma: no cover

@@ -59,6 +59,7 @@
 #include "../../include/paddle3d_amd.h"
 #include "block_topk.hpp"
 #include "common.hpp"
+#include "head_math.hpp"
 #include "libm_exact.hpp"
 #include "nms_kernels.hpp"
 
@@ -70,10 +71,7 @@ using namespace pd3;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr uint32_t kOneBits = 0x3F800000u;    // bits of 1.0f
-constexpr uint32_t kKeyNaN = kOneBits + 1u;   // a NaN score: after every number
-constexpr uint32_t kKeyAll = kOneBits + 2u;   // a cut-off that takes every key
-constexpr int kKeyBits = 30;
+constexpr uint32_t kKeyNaN = kScoreKeyOne + 1u;  // a NaN score: after every number
 constexpr int kChunkRows = 192;               // class rows of one chunk of anchors
 constexpr int kChunkTiles = kChunkRows / 16;
 constexpr int kLogitStride = kChunkRows + 1;
@@ -85,12 +83,7 @@ struct A3dShape {
   int apc, tiles_full;  // anchors per chunk, tiles of a full chunk
 };
 
-__device__ __forceinline__ uint32_t score_key(float s) { return s == s ? kOneBits - __float_as_uint(s) : kKeyNaN; }
-
-template <class Tab>
-__device__ __forceinline__ float sigmoid_exact(float x, Tab tab) {
-  return 1.0f / (1.0f + lm::expf_with(-x, tab));
-}
+__device__ __forceinline__ uint32_t score_key(float s) { return s == s ? kScoreKeyOne - __float_as_uint(s) : kKeyNaN; }
 
 // ---- a. dense class-score maximum ------------------------------------------------------------------------------------
 constexpr int kWaveTiles = 2;                        // 16-pixel tiles of one wave: a weight fragment feeds two MFMAs
@@ -102,7 +95,7 @@ __global__ __launch_bounds__(256) void a3d_dense_max_kernel(const float* __restr
                                                             float* __restrict__ max_score) {
   __shared__ uint64_t etab[32];
   __shared__ float logits[4][16][kLogitStride];
-  if (threadIdx.x < 32) etab[threadIdx.x] = lm::exp2f_tab(threadIdx.x);
+  lm::exp2f_tab_fill(etab);
   __syncthreads();
   const auto tab = [&](int i) { return etab[i]; };
   const int lane = lane_id(), wave = wave_id();
@@ -196,7 +189,7 @@ __global__ __launch_bounds__(256) void a3d_dense_max_kernel(const float* __restr
 __global__ __launch_bounds__(256) void a3d_maps_max_kernel(const float* __restrict__ cls, A3dShape sh,
                                                            float* __restrict__ max_score) {
   __shared__ uint64_t etab[32];
-  if (threadIdx.x < 32) etab[threadIdx.x] = lm::exp2f_tab(threadIdx.x);
+  lm::exp2f_tab_fill(etab);
   __syncthreads();
   const auto tab = [&](int i) { return etab[i]; };
   const int pix = blockIdx.x * blockDim.x + threadIdx.x, a = blockIdx.y, b = blockIdx.z;
@@ -234,7 +227,7 @@ __global__ __launch_bounds__(kTopkThreads) void a3d_topk_kernel(const float* __r
       for (int i = t; i < N; i += kTopkThreads) f(key(i));
     }
   };
-  const TopkCut cut = N > K ? block_topk_cut(K, kKeyBits, hist, scr, visit) : TopkCut{kKeyAll, 0};
+  const TopkCut cut = N > K ? block_topk_cut(K, kScoreKeyBits, hist, scr, visit) : TopkCut{kScoreKeyAll, 0};
   block_topk_compact(cut, N, key, [](int i, int) { return (uint32_t)i; }, list, scr);
   // topk_inds.sort(): the taken anchors in ascending index
   const unsigned long long e = list[t];
@@ -267,7 +260,7 @@ __global__ __launch_bounds__(256) void a3d_rows_kernel(const float* __restrict__
                                                        const int* __restrict__ sel, A3dShape sh, A3dCand cd) {
   __shared__ uint64_t etab[32];
   __shared__ float vals[4][3][16];
-  if (threadIdx.x < 32) etab[threadIdx.x] = lm::exp2f_tab(threadIdx.x);
+  lm::exp2f_tab_fill(etab);
   __syncthreads();
   const auto tab = [&](int i) { return etab[i]; };
   const int lane = lane_id(), wave = wave_id();
@@ -420,7 +413,7 @@ __global__ __launch_bounds__(kTopkThreads) void a3d_output_kernel(A3dCand cd, in
     const auto visit = [&](auto f) {
       for (int i = t; i < total; i += kTopkThreads) f(kg[i]);
     };
-    const TopkCut cut = block_topk_cut(max_num, kKeyBits, hist, scr, visit);
+    const TopkCut cut = block_topk_cut(max_num, kScoreKeyBits, hist, scr, visit);
     block_topk_compact(cut, total, key, [](int i, int) { return (uint32_t)i; }, list, scr);
     block_topk_sort(list, max_num);
     e = (int)(uint32_t)list[t];

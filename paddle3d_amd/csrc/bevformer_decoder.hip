@@ -90,7 +90,7 @@ __global__ void __launch_bounds__(kMhaThreads) mha_kernel(const float* __restric
                                                           int Nk, int M, int d, int QB, int SN, float scale) {
   extern __shared__ float lds[];
   __shared__ uint64_t etab[32];  // expf's table: a read per call from memory is a global load the polynomial waits for
-  if (threadIdx.x < 32) etab[threadIdx.x] = lm::exp2f_tab(threadIdx.x);
+  lm::exp2f_tab_fill(etab);
   const auto tab = [&](int i) { return etab[i]; };
   float* S = lds;               // [16][SN] scores, then weights
   float* Qs = lds + 16 * SN;    // [16][d + kQPad] scaled queries
@@ -304,7 +304,7 @@ __global__ void __launch_bounds__(kTopkThreads) nms_free_decode_kernel(DecodeCfg
   __shared__ unsigned long long list[kTopkMaxK];
   __shared__ int scr[kTopkScratch];
   __shared__ uint64_t etab[32];  // expf's table (libm_exact.hpp expf_with)
-  if (threadIdx.x < 32) etab[threadIdx.x] = lm::exp2f_tab(threadIdx.x);
+  lm::exp2f_tab_fill(etab);
   __syncthreads();
   const auto tab = [&](int i) { return etab[i]; };
   const int frame = blockIdx.x, tid = threadIdx.x;

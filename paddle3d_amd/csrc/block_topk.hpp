@@ -25,11 +25,16 @@ struct TopkCut {
   int r;
 };
 
+// A score in [0, 1] as a key: bits(1.0f) - bits(score), ascending key = descending score.
+constexpr uint32_t kScoreKeyOne = 0x3F800000u;        // bits of 1.0f
+constexpr uint32_t kScoreKeyAll = kScoreKeyOne + 2u;  // a cut-off that takes every key (one above a caller's NaN key)
+constexpr int kScoreKeyBits = 30;                     // bits such a key can have
+
 // Bits a score key bits(1.0f) - bits(score) can have when the scores taken are above (or at) `score_threshold`.
 static inline int topk_key_bits(float score_threshold) {
-  constexpr uint32_t one = 0x3F800000u;  // bits of 1.0f
   const uint32_t thr_bits = __builtin_bit_cast(uint32_t, score_threshold);
-  return 32 - __builtin_clz(score_threshold > 0.f && thr_bits < one ? one - thr_bits : one);  // 1 .. 30
+  const bool below_one = score_threshold > 0.f && thr_bits < kScoreKeyOne;
+  return 32 - __builtin_clz(below_one ? kScoreKeyOne - thr_bits : kScoreKeyOne);  // 1 .. 30
 }
 
 // Cut-off of the K smallest keys.  `visit(f)` calls f(key) for every key of this thread that can be taken (any split

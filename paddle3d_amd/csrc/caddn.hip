@@ -51,11 +51,14 @@
 // No atomics, no host synchronisation, 64-bit offsets into every tensor.  tests/golden/caddn_numpy.py restates all of
 // this in the same order.
 #include "common.hpp"
+#include "head_math.hpp"
 #include "libm_exact.hpp"
 
 #include <cmath>
 
 namespace {
+
+using pd3::relu_keep_nan;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -257,7 +260,6 @@ __global__ __launch_bounds__(kThreads) void frustum_to_voxel_kernel(const float*
 }
 
 // ---- frustum_to_bev -------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float relu_keep_nan(float v) { return v != v ? v : (v > 0.f ? v : 0.f); }
 
 template <int NT>
 __global__ __launch_bounds__(kThreads) void frustum_to_bev_kernel(

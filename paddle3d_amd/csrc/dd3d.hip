@@ -71,9 +71,10 @@
 //   f. nms_sweep_kernel   (nms_kernels.hpp) grid (B)
 //   g. dd_finish_kernel   grid (B), kTopkThreads: the post-NMS cut (block_topk_cut on the 2D scores), rows and counts
 // No atomics but the histogram's in LDS, no host synchronisation, 64-bit offsets.
-#include "../../include/paddle3d_amd_dd3d.h"
+#include "../../include/paddle3d_amd.h"
 #include "block_topk.hpp"
 #include "common.hpp"
+#include "head_math.hpp"
 #include "libm_exact.hpp"
 #include "nms_kernels.hpp"
 
@@ -83,10 +84,7 @@ namespace {
 
 using namespace pd3;
 
-constexpr uint32_t kOneBits = 0x3F800000u;   // bits of 1.0f
-constexpr uint32_t kKeyAll = kOneBits + 2u;  // a cut-off that takes every candidate's key
-constexpr uint32_t kNoKey = 0xFFFFFFFFu;     // no candidate: above 2^kKeyBits, never counted, never taken
-constexpr int kKeyBits = 30;
+constexpr uint32_t kNoKey = 0xFFFFFFFFu;  // no candidate: above 2^kScoreKeyBits, never counted, never taken
 constexpr int kMaxLevels = 8, kMaxC = 512, kMaxClasses = 16, kRow = 20, kVals = 15;
 constexpr int kGroup = 16, kDecodeThreads = 256, kRankThreads = 256, kKeyThreads = 256;
 constexpr size_t kLdsBytes = 160 * 1024;  // LDS of a gfx950 CU
@@ -115,17 +113,10 @@ struct DdWeights {
   const float *w2d, *b2d, *w3d, *b3d, *scales, *intrinsics, *canon;
 };
 
-template <class Tab>
-__device__ __forceinline__ float sigmoid_exact(float x, Tab tab) {
-  return 1.0f / (1.0f + lm::expf_with(-x, tab));
-}
-
-__device__ __forceinline__ float relu_keep_nan(float v) { return (v > 0.0f || v != v) ? v : 0.0f; }
-
 // ---- a. keys: grid (ceil(max HW / 256), levels, B) ------------------------------------------------------------------
 __global__ __launch_bounds__(kKeyThreads) void dd_keys_kernel(DdLevels lvs, DdCfg cf, uint32_t* __restrict__ keys) {
   __shared__ uint64_t etab[32];
-  if (threadIdx.x < 32) etab[threadIdx.x] = lm::exp2f_tab(threadIdx.x);
+  lm::exp2f_tab_fill(etab);
   __syncthreads();
   const auto tab = [&](int i) { return etab[i]; };
   const DdLevel& lv = lvs.lv[blockIdx.y];
@@ -139,7 +130,7 @@ __global__ __launch_bounds__(kKeyThreads) void dd_keys_kernel(DdLevels lvs, DdCf
     const float sl = sigmoid_exact(lg[(int64_t)c * HW], tab);
     const float s = sl * sc;
     const bool cand = ((cf.flags & kFlagCtr) ? s > cf.thr : sl > cf.thr) && s == s;
-    kb[c] = cand ? kOneBits - __float_as_uint(s) : kNoKey;
+    kb[c] = cand ? kScoreKeyOne - __float_as_uint(s) : kNoKey;
   }
 }
 
@@ -165,7 +156,7 @@ __global__ __launch_bounds__(kTopkThreads) void dd_select_kernel(DdLevels lvs, D
     for (int i = t; i < N; i += kTopkThreads) f(kb[i]);
   };
   // (uniform) more candidates than K: the radix select, whose precondition that is; else every candidate is taken
-  const TopkCut cut = ncand > K ? block_topk_cut(K, kKeyBits, hist, scr, visit) : TopkCut{kKeyAll, 0};
+  const TopkCut cut = ncand > K ? block_topk_cut(K, kScoreKeyBits, hist, scr, visit) : TopkCut{kScoreKeyAll, 0};
   block_topk_compact(cut, N, key, [](int i, int) { return (uint32_t)i; }, list, scr);
   block_topk_sort(list, K);
   if (t < K) sel[((int64_t)b * cf.L + l) * K + t] = list[t];
@@ -173,21 +164,6 @@ __global__ __launch_bounds__(kTopkThreads) void dd_select_kernel(DdLevels lvs, D
 }
 
 // ---- c. predictors and decode: grid (ceil(K / 16), levels, B), 256 threads ----------------------------------------------
-// the inverse of a row-major 3x3 in double by the adjugate, rounded to fp32
-__device__ void inverse3(const float* __restrict__ m, float* out) {
-  const double a = m[0], b = m[1], c = m[2], d = m[3], e = m[4], f = m[5], g = m[6], h = m[7], i = m[8];
-  const double c00 = e * i - f * h, c01 = c * h - b * i, c02 = b * f - c * e;
-  const double c10 = f * g - d * i, c11 = a * i - c * g, c12 = c * d - a * f;
-  const double c20 = d * h - e * g, c21 = b * g - a * h, c22 = a * e - b * d;
-  const double det = (a * c00 + b * c10) + c * c20;
-  const double adj[9] = {c00, c01, c02, c10, c11, c12, c20, c21, c22};
-  for (int k = 0; k < 9; ++k) out[k] = (float)(adj[k] / det);
-}
-
-__device__ __forceinline__ float mat3_row(const float* m, int r, float p0, float p1, float p2) {
-  return (m[3 * r] * p0 + m[3 * r + 1] * p1) + m[3 * r + 2] * p2;
-}
-
 __device__ __forceinline__ float norm3(float a, float b, float c) { return sqrtf((a * a + b * b) + c * c); }
 __device__ __forceinline__ float norm4(float a, float b, float c, float d) {
   return sqrtf(((a * a + b * b) + c * c) + d * d);
@@ -224,7 +200,7 @@ __global__ __launch_bounds__(kDecodeThreads) void dd_decode_kernel(DdLevels lvs,
   const int e0 = blockIdx.x * (kDecodeThreads / kGroup);
   if (e0 >= cnt) return;  // the whole block
   const DdLevel& lv = lvs.lv[l];
-  if (t < 32) etab[t] = lm::exp2f_tab(t);
+  lm::exp2f_tab_fill(etab);
   if (t == 64 && cf.has3d) inverse3(wt.intrinsics + (int64_t)b * 9, inv);
   const auto tab = [&](int i) { return etab[i]; };
   const int g = t / kGroup, j = t % kGroup, k = e0 + g;
@@ -291,7 +267,7 @@ __global__ __launch_bounds__(kDecodeThreads) void dd_decode_kernel(DdLevels lvs,
   __syncthreads();
   if (!live || j != 0) return;
   const float* v = vals[g];
-  const float s = __uint_as_float(kOneBits - (uint32_t)(ent >> 32));
+  const float s = __uint_as_float(kScoreKeyOne - (uint32_t)(ent >> 32));
   const float score = sqrtf(s);
   const int half = (cf.flags & kFlagHalf) ? lv.stride / 2 : 0;
   const float lx = (float)(x * lv.stride + half), ly = (float)(y * lv.stride + half);
@@ -373,7 +349,7 @@ __global__ __launch_bounds__(kDecodeThreads) void dd_decode_kernel(DdLevels lvs,
 #pragma unroll
   for (int a = 0; a < kRow; ++a) ro[a] = out[a];
   const float order = cf.has3d ? s3 : score;
-  const uint32_t k31 = order != order ? 0x7FFFFFFFu : kOneBits - __float_as_uint(order);
+  const uint32_t k31 = order != order ? 0x7FFFFFFFu : kScoreKeyOne - __float_as_uint(order);
   skey[pos] = cls < cf.cats ? ((unsigned long long)k31 << 33) | ((unsigned long long)l << 30) | (unsigned long long)idx
                             : ~0ull;
 }
@@ -459,13 +435,13 @@ __global__ __launch_bounds__(kTopkThreads) void dd_finish_kernel(DdCfg cf, const
   const int nk = min(nkeep[b], cf.cap);
   const int32_t* kp = keep + (int64_t)b * cf.cap;
   const float* sr = srow + (int64_t)b * cf.cap * kRow;
-  const auto key = [&](int i) { return kOneBits - __float_as_uint(sr[(int64_t)kp[i] * kRow + 4]); };
+  const auto key = [&](int i) { return kScoreKeyOne - __float_as_uint(sr[(int64_t)kp[i] * kRow + 4]); };
   uint32_t cutoff = kNoKey;  // rows with key <= cutoff stay
   if (cf.P > 0 && nk > cf.P) {  // (uniform)
     const auto visit = [&](auto f) {
       for (int i = t; i < nk; i += kTopkThreads) f(key(i));
     };
-    const TopkCut cut = block_topk_cut(cf.P, kKeyBits, hist, scr, visit);
+    const TopkCut cut = block_topk_cut(cf.P, kScoreKeyBits, hist, scr, visit);
     if (cut.r > 0) {
       cutoff = cut.kc;
     } else {  // the P keys below kc are taken: the cut-off is the largest of them

@@ -59,6 +59,7 @@
 // No FMA but the MFMA chain (-ffp-contract=off).  tests/golden/iassd_numpy.py restates both in the same order and both
 // equal it bit for bit.
 #include "common.hpp"
+#include "head_math.hpp"
 #include "libm_exact.hpp"
 #include "pointnet2_common.hpp"
 
@@ -67,6 +68,7 @@
 namespace {
 
 using pd3::pn2::ballot_rank;
+using pd3::relu_keep_nan;
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / pd3::kWave;
@@ -78,7 +80,6 @@ constexpr int kMaxBlocks = 2048;  // 8 per CU: the workgroups walk the rest of t
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ float relu_keep_nan(float v) { return v != v ? v : (v > 0.f ? v : 0.f); }
 __device__ __forceinline__ float max_keep_nan(float acc, float v) { return (v > acc || v != v) ? v : acc; }
 
 // One Conv / BN / ReLU layer over the pass's live row tiles: in [64, cin] (row stride ins) -> out [64, cout] (row

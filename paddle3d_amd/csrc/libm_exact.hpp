@@ -183,6 +183,18 @@ PD3_HD uint64_t exp2f_tab(int i) {
   return t[i];
 }
 
+#if defined(__HIPCC__)
+// The table into a workgroup's LDS array, one entry per thread of the first 32 (see expf_with).  No barrier: the caller
+// places its own before the first read.  The slot's address is formed before the table is read: in that order the
+// kernels' code is, instruction for instruction, what the statement written out in each of them gave.
+__device__ __forceinline__ void exp2f_tab_fill(uint64_t* etab) {
+  if (threadIdx.x < 32) {
+    uint64_t* const slot = etab + threadIdx.x;
+    *slot = exp2f_tab(threadIdx.x);
+  }
+}
+#endif
+
 // |x| >= 88 or NaN: the arguments expf treats before its polynomial
 PD3_HD bool expf_is_special(float x) { return ((f2u(x) >> 20) & 0x7ffu) >= 0x42bu; }
 

@@ -94,7 +94,7 @@ __global__ void __launch_bounds__(kStreamThreads) mha_stream_kernel(const float*
   __shared__ float wmx[kStreamWaves][16], t0s[16], sums[16];
   __shared__ float P[16][kWave + 1];
   __shared__ float A[kStreamWaves][16][AS];
-  if (threadIdx.x < 32) etab[threadIdx.x] = lm::exp2f_tab(threadIdx.x);
+  lm::exp2f_tab_fill(etab);
   const auto tab = [&](int i) { return etab[i]; };
   const int tid = threadIdx.x, lane = lane_id(), wave = wave_id();
   const int col = lane & 15, g = lane >> 4;

@@ -213,7 +213,7 @@ __global__ __launch_bounds__(kTopkThreads) void cp_topk_kernel(CpHeads h, CpCfg 
   uint64_t* etab = reinterpret_cast<uint64_t*>(scr + kTopkScratch);                                // [32]: expf's table
   unsigned char* cls = reinterpret_cast<unsigned char*>(etab + 32);                          // [hw]: best class of a cell
   const int set = blockIdx.x, sets = gridDim.x;
-  if (threadIdx.x < 32) etab[threadIdx.x] = lm::exp2f_tab((int)threadIdx.x);
+  lm::exp2f_tab_fill(etab);
   __syncthreads();
   // ---- keys of all cells (cp_cell_key, kTopkBatch cells of a thread at a time) ---------------------------------
   // A cell is a chain of dependent reads (head values -> expf's table -> key); one cell after the other, 16 such

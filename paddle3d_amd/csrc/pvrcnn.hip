@@ -42,6 +42,7 @@
 // tests/golden/pv_rcnn_numpy.py restates both in the same order; bev_interpolate equals it bit for bit, and so does
 // stack_sa_pool against the restatement's fp32 fmaf-chain form.
 #include "common.hpp"
+#include "head_math.hpp"
 #include "pointnet2_common.hpp"
 
 #include <cmath>
@@ -49,6 +50,7 @@
 namespace {
 
 using pd3::pn2::ballot_rank;
+using pd3::relu_keep_nan;
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / pd3::kWave;
@@ -58,7 +60,6 @@ constexpr int kMaxBlocks = 4096;     // 16 per CU: the waves walk the rest of th
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ float relu_keep_nan(float v) { return v != v ? v : (v > 0.f ? v : 0.f); }
 __device__ __forceinline__ float max_keep_nan(float acc, float v) { return (v > acc || v != v) ? v : acc; }
 
 // The wave's LDS stores before, its LDS loads after.

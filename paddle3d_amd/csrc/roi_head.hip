@@ -43,6 +43,7 @@
 //
 // tests/golden/roi_head_numpy.py restates all of this in the same order; the device results equal it bit for bit.
 #include "common.hpp"
+#include "head_math.hpp"
 #include "libm_exact.hpp"
 #include "nms_kernels.hpp"
 #include "pointnet2_common.hpp"
@@ -59,8 +60,6 @@ using pd3::pn2::ballot_rank;
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / pd3::kWave;
 constexpr int kMaxSample = 64;  // a row of idx is one wave's lanes
-
-__device__ __forceinline__ float relu_keep_nan(float v) { return v != v ? v : (v > 0.f ? v : 0.f); }
 
 template <int C1>
 __global__ __launch_bounds__(kThreads) void voxel_pool_kernel(

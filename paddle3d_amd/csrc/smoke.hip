@@ -51,9 +51,10 @@
 //   c. smoke_select_kernel  grid (B), 1024 threads: keys (the 3x3 peak test applied while the heat map is read), the
 //      exact top-K (block_topk.hpp), the ten regression values (lazy: thread = (entry, row)), the decode, rows, count
 // No atomics but the histogram's in LDS, no host synchronisation, 64-bit offsets.
-#include "../../include/paddle3d_amd_smoke.h"
+#include "../../include/paddle3d_amd.h"
 #include "block_topk.hpp"
 #include "common.hpp"
+#include "head_math.hpp"
 #include "libm_exact.hpp"
 
 #include <algorithm>
@@ -62,9 +63,6 @@ namespace {
 
 using namespace pd3;
 
-constexpr uint32_t kOneBits = 0x3F800000u;   // bits of 1.0f
-constexpr uint32_t kKeyAll = kOneBits + 2u;  // a cut-off that takes every key
-constexpr int kKeyBits = 30;
 constexpr int kMaxC = 512, kMaxClasses = 16, kMaxK = 1024, kReg = 10, kCols = 14;
 constexpr int kStatThreads = 1024, kClassThreads = 64;
 constexpr float kPi = 3.14159f;  // the reference's PI
@@ -78,13 +76,6 @@ struct SmokeShape {
 struct SmokeCam {
   const float *Ks, *trans, *image_size, *depth_ref, *dim_ref;
 };
-
-template <class Tab>
-__device__ __forceinline__ float sigmoid_exact(float x, Tab tab) {
-  return 1.0f / (1.0f + lm::expf_with(-x, tab));
-}
-
-__device__ __forceinline__ float relu_keep_nan(float v) { return (v > 0.0f || v != v) ? v : 0.0f; }
 
 // ---- a. tables: grid (G, B, branches) ---------------------------------------------------------------------------------
 __device__ __forceinline__ double stats_fold(double v, double* p) {
@@ -147,7 +138,7 @@ __global__ __launch_bounds__(kClassThreads) void smoke_class_kernel(const float*
   __shared__ uint64_t etab[32];
   __shared__ float4 prm[kMaxC];  // mean, rstd, gamma, beta of a channel
   const int b = blockIdx.y;
-  if (threadIdx.x < 32) etab[threadIdx.x] = lm::exp2f_tab(threadIdx.x);
+  lm::exp2f_tab_fill(etab);
   const int cpg = sh.C / sh.G;
   for (int c = threadIdx.x; c < sh.C; c += blockDim.x) {
     const int g = c / cpg;
@@ -182,21 +173,6 @@ __global__ __launch_bounds__(kClassThreads) void smoke_class_kernel(const float*
 }
 
 // ---- c. selection and decode: grid (B), kTopkThreads ----------------------------------------------------------------
-// the inverse of a row-major 3x3 in double by the adjugate, rounded to fp32
-__device__ void inverse3(const float* __restrict__ m, float* out) {
-  const double a = m[0], b = m[1], c = m[2], d = m[3], e = m[4], f = m[5], g = m[6], h = m[7], i = m[8];
-  const double c00 = e * i - f * h, c01 = c * h - b * i, c02 = b * f - c * e;
-  const double c10 = f * g - d * i, c11 = a * i - c * g, c12 = c * d - a * f;
-  const double c20 = d * h - e * g, c21 = b * g - a * h, c22 = a * e - b * d;
-  const double det = (a * c00 + b * c10) + c * c20;
-  const double adj[9] = {c00, c01, c02, c10, c11, c12, c20, c21, c22};
-  for (int k = 0; k < 9; ++k) out[k] = (float)(adj[k] / det);
-}
-
-__device__ __forceinline__ float mat3_row(const float* m, int r, float p0, float p1, float p2) {
-  return (m[3 * r] * p0 + m[3 * r + 1] * p1) + m[3 * r + 2] * p2;
-}
-
 __device__ __forceinline__ float clip_keep_nan(float v, float hi) { return v < 0.0f ? 0.0f : (v > hi ? hi : v); }
 
 template <bool LAZY>
@@ -218,7 +194,7 @@ __global__ __launch_bounds__(kTopkThreads) void smoke_select_kernel(const float*
   __shared__ float inv[2][9];
   const int b = blockIdx.x, t = threadIdx.x;
   const int N = sh.nc * sh.HW, K = sh.K;
-  if (t < 32) etab[t] = lm::exp2f_tab(t);
+  lm::exp2f_tab_fill(etab);
   if (t == 64) inverse3(cam.Ks + (int64_t)b * 9, inv[0]);
   if (t == 128 && sh.mode == 0) inverse3(cam.trans + (int64_t)b * 9, inv[1]);
   const auto tab = [&](int i) { return etab[i]; };
@@ -235,7 +211,7 @@ __global__ __launch_bounds__(kTopkThreads) void smoke_select_kernel(const float*
         const int yy = y + dy, xx = x + dx;
         if (yy >= 0 && yy < sh.H && xx >= 0 && xx < sh.W && pl[yy * sh.W + xx] > h) peak = false;
       }
-    kb[i] = kOneBits - __float_as_uint(peak ? h : 0.0f);
+    kb[i] = kScoreKeyOne - __float_as_uint(peak ? h : 0.0f);
   }
   __syncthreads();  // the block's keys are in memory
   const auto key = [&](int i) { return kb[i]; };
@@ -243,7 +219,7 @@ __global__ __launch_bounds__(kTopkThreads) void smoke_select_kernel(const float*
 #pragma unroll 4
     for (int i = t; i < N; i += kTopkThreads) f(kb[i]);
   };
-  const TopkCut cut = N > K ? block_topk_cut(K, kKeyBits, hist, scr, visit) : TopkCut{kKeyAll, 0};
+  const TopkCut cut = N > K ? block_topk_cut(K, kScoreKeyBits, hist, scr, visit) : TopkCut{kScoreKeyAll, 0};
   block_topk_compact(cut, N, key, [](int i, int) { return (uint32_t)i; }, list, scr);
   block_topk_sort(list, K);
   // the ten regression values of every entry
@@ -279,7 +255,7 @@ __global__ __launch_bounds__(kTopkThreads) void smoke_select_kernel(const float*
   if (t < K) {
     const unsigned long long ent = list[t];
     const int i = min((int)(uint32_t)ent, N - 1);
-    const float score = __uint_as_float(kOneBits - (uint32_t)(ent >> 32));
+    const float score = __uint_as_float(kScoreKeyOne - (uint32_t)(ent >> 32));
     const int cls = i / sh.HW, p = i - cls * sh.HW, yi = p / sh.W, xi = p - yi * sh.W;
     const float xs = (float)xi, ys = (float)yi;
     float r[kReg];

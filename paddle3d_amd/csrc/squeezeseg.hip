@@ -95,7 +95,7 @@ __global__ void __launch_bounds__(kSacThreads) sac_isk_kernel(const float* __res
                                                               int H, int W, int XT, int64_t segments, int vec) {
   constexpr int C = 16 * CT, NT = 9 * CT, CTP = CT / OS;
   __shared__ uint64_t etab[32];  // expf's table (libm_exact.hpp expf_with)
-  if (threadIdx.x < 32) etab[threadIdx.x] = lm::exp2f_tab(threadIdx.x);
+  lm::exp2f_tab_fill(etab);
   __syncthreads();
   const auto tab = [&](int i) { return etab[i]; };
   const int lane = lane_id(), col = lane & 15, g = lane >> 4;

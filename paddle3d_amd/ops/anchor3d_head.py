@@ -22,7 +22,7 @@ import ctypes as C
 
 import torch
 
-from ._common import check, lib, ptr, stream_ptr, workspace
+from ._common import check, gpu_tensor, lib, ptr, stream_ptr, workspace
 
 __all__ = ["anchor3d_supported", "pack_cls_weight", "unpack_cls_weight", "anchor3d_head_forward",
            "anchor3d_get_bboxes", "aligned_anchor3d_grid", "CHUNK_ROWS", "MAX_K"]
@@ -112,18 +112,6 @@ def aligned_anchor3d_grid(ranges, sizes, rotations, custom_values, featmap_size,
     return out.reshape(-1, out.shape[-1])
 
 
-def _gpu(what, t, dev=None, shape=None):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"Unsupported device type for {_OP} operator.")
-    if t.dtype != torch.float32:
-        raise RuntimeError(f"{_OP}: {what} must be torch.float32, got {t.dtype}")
-    if dev is not None and t.device != dev:
-        raise RuntimeError(f"{_OP}: {what} is on {t.device}, expected {dev}")
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise RuntimeError(f"{_OP}: {what} must be {tuple(shape)}, got {tuple(t.shape)}")
-    return t.contiguous()
-
-
 def _outputs(b, max_num, cs, dev):
     return (torch.empty((b, max_num, cs), dtype=torch.float32, device=dev),
             torch.empty((b, max_num), dtype=torch.float32, device=dev),
@@ -140,25 +128,25 @@ def anchor3d_head_forward(feat, cls_weight_packed, cls_bias, reg_weight, reg_bia
                           num_classes, nms_pre, max_num, score_thr, nms_thr, dir_offset=0.0, dir_limit_offset=1.0):
     """feat [B, C, H, W]; cls_weight_packed from pack_cls_weight; reg_weight [A * code_size, C(, 1, 1)], dir_weight
     [A * 2, C(, 1, 1)] and the biases as the convolutions hold them; anchors [H * W * A, code_size]."""
-    feat = _gpu("feat", feat)
+    feat = gpu_tensor(_OP, "feat", feat)
     dev = feat.device
     if feat.dim() != 4:
         raise RuntimeError(f"{_OP}: feat must be [B, C, H, W], got {tuple(feat.shape)}")
     b, c, h, w = (int(s) for s in feat.shape)
     nc = int(num_classes)
-    anchors = _gpu("anchors", anchors, dev)
+    anchors = gpu_tensor(_OP, "anchors", anchors, dev=dev)
     if anchors.dim() != 2 or h * w == 0 or anchors.shape[0] % (h * w):
         raise RuntimeError(f"{_OP}: anchors {tuple(anchors.shape)} do not fit a {h} x {w} map")
     a, cs = int(anchors.shape[0]) // (h * w), int(anchors.shape[1])
     if not anchor3d_supported(c, nc, a, cs, int(nms_pre), int(max_num), h * w * a):
         return None
     _, tiles = _chunks(a, nc)
-    wp = _gpu("cls_weight_packed", cls_weight_packed, dev, (tiles, c // 4, 64))
-    cb = _gpu("cls_bias", cls_bias, dev, (a * nc,))
-    rw = _gpu("reg_weight", reg_weight.reshape(reg_weight.shape[0], -1), dev, (a * cs, c))
-    rb = _gpu("reg_bias", reg_bias, dev, (a * cs,))
-    dw = _gpu("dir_weight", dir_weight.reshape(dir_weight.shape[0], -1), dev, (a * 2, c))
-    db = _gpu("dir_bias", dir_bias, dev, (a * 2,))
+    wp = gpu_tensor(_OP, "cls_weight_packed", cls_weight_packed, dev=dev, shape=(tiles, c // 4, 64))
+    cb = gpu_tensor(_OP, "cls_bias", cls_bias, dev=dev, shape=(a * nc,))
+    rw = gpu_tensor(_OP, "reg_weight", reg_weight.reshape(reg_weight.shape[0], -1), dev=dev, shape=(a * cs, c))
+    rb = gpu_tensor(_OP, "reg_bias", reg_bias, dev=dev, shape=(a * cs,))
+    dw = gpu_tensor(_OP, "dir_weight", dir_weight.reshape(dir_weight.shape[0], -1), dev=dev, shape=(a * 2, c))
+    db = gpu_tensor(_OP, "dir_bias", dir_bias, dev=dev, shape=(a * 2,))
     L = lib()
     outs = _outputs(b, int(max_num), cs, dev)
     ws = workspace(L.pd3_anchor3d_head_workspace(b, h, w, a, nc, cs, int(nms_pre)), dev)
@@ -176,19 +164,19 @@ def anchor3d_get_bboxes(cls_score, bbox_pred, dir_cls_pred, anchors, num_classes
                         dir_offset=0.0, dir_limit_offset=1.0):
     """cls_score [B, A * nc, H, W], bbox_pred [B, A * code_size, H, W], dir_cls_pred [B, A * 2, H, W] (the head's
     three maps), anchors [H * W * A, code_size]."""
-    cls_score = _gpu("cls_score", cls_score)
+    cls_score = gpu_tensor(_OP, "cls_score", cls_score)
     dev = cls_score.device
     nc = int(num_classes)
     if cls_score.dim() != 4 or cls_score.shape[1] % nc:
         raise RuntimeError(f"{_OP}: cls_score must be [B, A * {nc}, H, W], got {tuple(cls_score.shape)}")
     b, ch, h, w = (int(s) for s in cls_score.shape)
     a = ch // nc
-    anchors = _gpu("anchors", anchors, dev)
+    anchors = gpu_tensor(_OP, "anchors", anchors, dev=dev)
     if anchors.dim() != 2 or anchors.shape[0] != h * w * a:
         raise RuntimeError(f"{_OP}: anchors must be [{h * w * a}, code_size], got {tuple(anchors.shape)}")
     cs = int(anchors.shape[1])
-    bbox_pred = _gpu("bbox_pred", bbox_pred, dev, (b, a * cs, h, w))
-    dir_cls_pred = _gpu("dir_cls_pred", dir_cls_pred, dev, (b, a * 2, h, w))
+    bbox_pred = gpu_tensor(_OP, "bbox_pred", bbox_pred, dev=dev, shape=(b, a * cs, h, w))
+    dir_cls_pred = gpu_tensor(_OP, "dir_cls_pred", dir_cls_pred, dev=dev, shape=(b, a * 2, h, w))
     if not anchor3d_supported(None, nc, a, cs, int(nms_pre), int(max_num), h * w * a):
         return None
     L = lib()

@@ -16,17 +16,11 @@ from __future__ import annotations
 
 import torch
 
-from ._common import check, lib, ptr, stream_ptr, workspace
+from ._common import check, gpu_tensor, lib, ptr, stream_ptr, workspace
 
 __all__ = ["assign_score_withk", "assign_score_withk_backward", "AssignScoreWithKFunction"]
 
 _OP = "assign_score_withk"
-
-
-def _gpu(t):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"Unsupported device type for {_OP} operator.")
-    return t
 
 
 def _check(scores, points, centers, knn_idx, grad_out=None):
@@ -34,8 +28,8 @@ def _check(scores, points, centers, knn_idx, grad_out=None):
     named = [("scores", scores), ("points", points), ("centers", centers), ("knn_idx", knn_idx)]
     if grad_out is not None:
         named.append(("grad_out", grad_out))
-    for _, t in named:
-        _gpu(t)
+    for what, t in named:
+        gpu_tensor(_OP, what, t, dtype=None, contiguous=False)
     for what, t in named[:3] + named[4:]:
         if t.dtype != torch.float32:
             raise RuntimeError(f"{_OP}: {what} must be float32, got {t.dtype}")
@@ -109,5 +103,5 @@ class AssignScoreWithKFunction(torch.autograd.Function):
 def assign_score_withk(scores, points, centers, knn_idx):
     """output [B, O, N] (the reference's op; differentiable in scores, points and centers)."""
     for t in (scores, points, centers, knn_idx):
-        _gpu(t)
+        gpu_tensor(_OP, None, t, dtype=None, contiguous=False)  # the device check alone
     return AssignScoreWithKFunction.apply(scores, points, centers, knn_idx)

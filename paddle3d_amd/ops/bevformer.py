@@ -23,7 +23,7 @@ from __future__ import annotations
 
 import torch
 
-from ._common import check, host_f32, lib, ptr, stream_ptr
+from ._common import check, gpu_tensor, host_f32, lib, ptr, stream_ptr
 
 __all__ = ["point_sampling", "spatial_cross_attention_sample", "temporal_self_attention_sample", "sca_supported",
            "tsa_supported", "MAX_CAMS", "MAX_LEVEL_POINTS"]
@@ -32,16 +32,6 @@ _OP = "bevformer"
 MAX_CAMS = 8
 MAX_LEVEL_POINTS = 32
 _UNSUPPORTED = -3
-
-
-def _gpu(what, t, dtype, dev=None):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"Unsupported device type for {_OP} operator.")
-    if t.dtype != dtype:
-        raise RuntimeError(f"{_OP}: {what} must be {dtype}, got {t.dtype}")
-    if dev is not None and t.device != dev:
-        raise RuntimeError(f"{_OP}: {what} is on {t.device}, expected {dev}")
-    return t.contiguous()
 
 
 def sca_supported(channels, num_levels, num_points, num_cams, num_anchors):
@@ -55,9 +45,9 @@ def tsa_supported(channels, num_levels, num_points):
 
 
 def point_sampling(ref_3d, lidar2img, pc_range, img_h, img_w):
-    ref_3d = _gpu("ref_3d", ref_3d, torch.float32)
+    ref_3d = gpu_tensor(_OP, "ref_3d", ref_3d, torch.float32)
     dev = ref_3d.device
-    lidar2img = _gpu("lidar2img", lidar2img, torch.float32, dev)
+    lidar2img = gpu_tensor(_OP, "lidar2img", lidar2img, torch.float32, dev)
     if ref_3d.dim() != 3 or int(ref_3d.shape[2]) != 3:
         raise RuntimeError(f"{_OP}: ref_3d must be [D, Q, 3], got {tuple(ref_3d.shape)}")
     if lidar2img.dim() != 4 or tuple(lidar2img.shape[2:]) != (4, 4):
@@ -81,8 +71,8 @@ def point_sampling(ref_3d, lidar2img, pc_range, img_h, img_w):
 
 
 def _levels(spatial_shapes, level_start_index, L, dev):
-    ss = _gpu("spatial_shapes", spatial_shapes, torch.int64, dev)
-    lsi = _gpu("level_start_index", level_start_index, torch.int64, dev)
+    ss = gpu_tensor(_OP, "spatial_shapes", spatial_shapes, torch.int64, dev)
+    lsi = gpu_tensor(_OP, "level_start_index", level_start_index, torch.int64, dev)
     if tuple(ss.shape) != (L, 2) or tuple(lsi.shape) != (L,):
         raise RuntimeError(f"{_OP}: spatial_shapes must be [{L}, 2] and level_start_index [{L}], got "
                            f"{tuple(ss.shape)} and {tuple(lsi.shape)}")
@@ -91,12 +81,12 @@ def _levels(spatial_shapes, level_start_index, L, dev):
 
 def spatial_cross_attention_sample(value, sampling_offsets, attention_logits, reference_points_cam, hit_bits,
                                    spatial_shapes, level_start_index, num_cams):
-    value = _gpu("value", value, torch.float32)
+    value = gpu_tensor(_OP, "value", value, torch.float32)
     dev = value.device
-    off = _gpu("sampling_offsets", sampling_offsets, torch.float32, dev)
-    logits = _gpu("attention_logits", attention_logits, torch.float32, dev)
-    ref = _gpu("reference_points_cam", reference_points_cam, torch.float32, dev)
-    bits = _gpu("hit_bits", hit_bits, torch.uint8, dev)
+    off = gpu_tensor(_OP, "sampling_offsets", sampling_offsets, torch.float32, dev)
+    logits = gpu_tensor(_OP, "attention_logits", attention_logits, torch.float32, dev)
+    ref = gpu_tensor(_OP, "reference_points_cam", reference_points_cam, torch.float32, dev)
+    bits = gpu_tensor(_OP, "hit_bits", hit_bits, torch.uint8, dev)
     if value.dim() != 4 or off.dim() != 6 or int(off.shape[-1]) != 2:
         raise RuntimeError(f"{_OP}: value must be [B*cams, S, M, C] and sampling_offsets [B, Q, M, L, P, 2], got "
                            f"{tuple(value.shape)} and {tuple(off.shape)}")
@@ -127,11 +117,11 @@ def spatial_cross_attention_sample(value, sampling_offsets, attention_logits, re
 
 def temporal_self_attention_sample(value, sampling_offsets, attention_logits, reference_points, spatial_shapes,
                                    level_start_index):
-    value = _gpu("value", value, torch.float32)
+    value = gpu_tensor(_OP, "value", value, torch.float32)
     dev = value.device
-    off = _gpu("sampling_offsets", sampling_offsets, torch.float32, dev)
-    logits = _gpu("attention_logits", attention_logits, torch.float32, dev)
-    ref = _gpu("reference_points", reference_points, torch.float32, dev)
+    off = gpu_tensor(_OP, "sampling_offsets", sampling_offsets, torch.float32, dev)
+    logits = gpu_tensor(_OP, "attention_logits", attention_logits, torch.float32, dev)
+    ref = gpu_tensor(_OP, "reference_points", reference_points, torch.float32, dev)
     if value.dim() != 4 or off.dim() != 7 or int(off.shape[-1]) != 2 or int(off.shape[3]) != 2:
         raise RuntimeError(f"{_OP}: value must be [B*2, S, M, C] and sampling_offsets [B, Q, M, 2, L, P, 2], got "
                            f"{tuple(value.shape)} and {tuple(off.shape)}")

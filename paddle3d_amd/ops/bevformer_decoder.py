@@ -24,7 +24,7 @@ import math
 
 import torch
 
-from ._common import check, host_f32, lib, ptr, stream_ptr
+from ._common import check, gpu_tensor, host_f32, lib, ptr, stream_ptr
 
 __all__ = ["multihead_attention", "decoder_cross_attention_sample", "nms_free_decode", "mha_supported",
            "dec_ca_supported", "MAX_HEAD_DIM", "MAX_KEYS", "MAX_LEVEL_POINTS", "MAX_NUM"]
@@ -37,16 +37,6 @@ MAX_NUM = 1024
 _UNSUPPORTED = -3
 
 
-def _gpu(what, t, dtype, dev=None):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"Unsupported device type for {_OP} operator.")
-    if t.dtype != dtype:
-        raise RuntimeError(f"{_OP}: {what} must be {dtype}, got {t.dtype}")
-    if dev is not None and t.device != dev:
-        raise RuntimeError(f"{_OP}: {what} is on {t.device}, expected {dev}")
-    return t.contiguous()
-
-
 def mha_supported(head_dim, num_key):
     """The kernel's shape predicate (it also wants 16-byte aligned tensors, which torch's allocations are)."""
     return head_dim >= 16 and head_dim % 16 == 0 and head_dim <= MAX_HEAD_DIM and num_key <= MAX_KEYS
@@ -57,10 +47,10 @@ def dec_ca_supported(channels, num_levels, num_points):
 
 
 def multihead_attention(q, k, v, num_heads):
-    q = _gpu("q", q, torch.float32)
+    q = gpu_tensor(_OP, "q", q, torch.float32)
     dev = q.device
-    k = _gpu("k", k, torch.float32, dev)
-    v = _gpu("v", v, torch.float32, dev)
+    k = gpu_tensor(_OP, "k", k, torch.float32, dev)
+    v = gpu_tensor(_OP, "v", v, torch.float32, dev)
     M = int(num_heads)
     if q.dim() != 3 or k.dim() != 3 or tuple(v.shape) != tuple(k.shape) or k.shape[0] != q.shape[0] or \
             k.shape[2] != q.shape[2]:
@@ -83,11 +73,11 @@ def multihead_attention(q, k, v, num_heads):
 
 def decoder_cross_attention_sample(value, sampling_offsets, attention_logits, reference_points, spatial_shapes,
                                    level_start_index):
-    value = _gpu("value", value, torch.float32)
+    value = gpu_tensor(_OP, "value", value, torch.float32)
     dev = value.device
-    off = _gpu("sampling_offsets", sampling_offsets, torch.float32, dev)
-    logits = _gpu("attention_logits", attention_logits, torch.float32, dev)
-    ref = _gpu("reference_points", reference_points, torch.float32, dev)
+    off = gpu_tensor(_OP, "sampling_offsets", sampling_offsets, torch.float32, dev)
+    logits = gpu_tensor(_OP, "attention_logits", attention_logits, torch.float32, dev)
+    ref = gpu_tensor(_OP, "reference_points", reference_points, torch.float32, dev)
     if value.dim() != 4 or off.dim() != 6 or int(off.shape[-1]) != 2:
         raise RuntimeError(f"{_OP}: value must be [B, S, M, C] and sampling_offsets [B, Q, M, L, P, 2], got "
                            f"{tuple(value.shape)} and {tuple(off.shape)}")
@@ -101,8 +91,8 @@ def decoder_cross_attention_sample(value, sampling_offsets, attention_logits, re
         raise RuntimeError(f"{_OP}: reference_points must be [{B}, {Q}, 1 or {L}, 2], got {tuple(ref.shape)}")
     if S < 1 or M < 1 or Ch < 1 or L < 1 or P < 1 or max(rows, S, Q) >= 2 ** 31:
         raise RuntimeError(f"{_OP}: bad sizes {(rows, S, M, Ch, L, Q, P)}")
-    ss = _gpu("spatial_shapes", spatial_shapes, torch.int64, dev)
-    lsi = _gpu("level_start_index", level_start_index, torch.int64, dev)
+    ss = gpu_tensor(_OP, "spatial_shapes", spatial_shapes, torch.int64, dev)
+    lsi = gpu_tensor(_OP, "level_start_index", level_start_index, torch.int64, dev)
     if tuple(ss.shape) != (L, 2) or tuple(lsi.shape) != (L,):
         raise RuntimeError(f"{_OP}: spatial_shapes must be [{L}, 2] and level_start_index [{L}], got "
                            f"{tuple(ss.shape)} and {tuple(lsi.shape)}")
@@ -116,9 +106,9 @@ def decoder_cross_attention_sample(value, sampling_offsets, attention_logits, re
 
 
 def nms_free_decode(cls_scores, bbox_preds, post_center_range, max_num, score_threshold=None, bottom_center=False):
-    cls = _gpu("cls_scores", cls_scores, torch.float32)
+    cls = gpu_tensor(_OP, "cls_scores", cls_scores, torch.float32)
     dev = cls.device
-    bbox = _gpu("bbox_preds", bbox_preds, torch.float32, dev)
+    bbox = gpu_tensor(_OP, "bbox_preds", bbox_preds, torch.float32, dev)
     if cls.dim() != 3 or bbox.dim() != 3 or tuple(bbox.shape[:2]) != tuple(cls.shape[:2]):
         raise RuntimeError(f"{_OP}: cls_scores must be [B, Q, K] and bbox_preds [B, Q, code], got {tuple(cls.shape)} "
                            f"and {tuple(bbox.shape)}")

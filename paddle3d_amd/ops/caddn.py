@@ -24,16 +24,15 @@ from __future__ import annotations
 
 import torch
 
-from ._common import check, host_f32, lib, ptr, stream_ptr, workspace
+from ._common import check, gpu_tensor, host_f32, lib, ptr, stream_ptr, workspace
 
 __all__ = ["frustum_grid", "frustum_to_voxel", "frustum_to_bev", "frustum_to_bev_supported", "DISC_MODES"]
 
 DISC_MODES = {"UD": 0, "LID": 1, "SID": 2}
 
 
-def _gpu(t, op, what, shape):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"Unsupported device type for {op} operator.")
+def _shaped(t, op, what, shape):
+    gpu_tensor(op, what, t, dtype=None, contiguous=False)
     if t.dtype != torch.float32:
         raise RuntimeError(f"{op}: {what} must be float32, got {t.dtype}")
     if t.dim() != len(shape) or any(s is not None and int(d) != s for d, s in zip(t.shape, shape)):
@@ -42,9 +41,9 @@ def _gpu(t, op, what, shape):
 
 
 def _calib(op, lidar_to_cam, cam_to_img, image_shape):
-    l2c = _gpu(lidar_to_cam, op, "lidar_to_cam", (None, 4, 4))
+    l2c = _shaped(lidar_to_cam, op, "lidar_to_cam", (None, 4, 4))
     B = int(l2c.shape[0])
-    c2i = _gpu(cam_to_img, op, "cam_to_img", (B, 3, 4))
+    c2i = _shaped(cam_to_img, op, "cam_to_img", (B, 3, 4))
     if not isinstance(image_shape, torch.Tensor) or not image_shape.is_cuda or tuple(image_shape.shape) != (B, 2):
         raise RuntimeError(f"{op}: image_shape must be a [{B}, 2] tensor on the GPU")
     if l2c.device != c2i.device or l2c.device != image_shape.device:
@@ -75,11 +74,11 @@ def frustum_grid(lidar_to_cam, cam_to_img, image_shape, grid_size, pc_min, voxel
 
 
 def _maps(op, image_features, depth_logits, B, D):
-    f = _gpu(image_features, op, "image_features", (B, None, None, None))
+    f = _shaped(image_features, op, "image_features", (B, None, None, None))
     C, h, w = (int(s) for s in f.shape[1:])
     if min(C, h, w) < 1:
         raise RuntimeError(f"{op}: empty image_features {tuple(f.shape)}")
-    p = _gpu(depth_logits, op, "depth_logits", (B, D + 1, h, w))
+    p = _shaped(depth_logits, op, "depth_logits", (B, D + 1, h, w))
     if p.device != f.device:
         raise RuntimeError(f"{op}: tensors on different devices")
     return f, p, C, h, w
@@ -109,9 +108,9 @@ def frustum_to_bev(image_features, depth_logits, lidar_to_cam, cam_to_img, image
     l2c, c2i, shp, B = _calib(op, lidar_to_cam, cam_to_img, image_shape)
     (X, Y, Z, mn, vs, mode, d0, d1), D = _grid_args(op, grid_size, pc_min, voxel_size, disc_cfg)
     f, p, C, h, w = _maps(op, image_features, depth_logits, B, D)
-    wt = _gpu(weight, op, "weight", (None, C * Z))
+    wt = _shaped(weight, op, "weight", (None, C * Z))
     CO = int(wt.shape[0])
-    sc, sh = _gpu(scale, op, "scale", (CO,)), _gpu(shift, op, "shift", (CO,))
+    sc, sh = _shaped(scale, op, "scale", (CO,)), _shaped(shift, op, "shift", (CO,))
     if CO < 1 or any(t.device != f.device for t in (wt, sc, sh, l2c)):
         raise RuntimeError(f"{op}: weight {tuple(wt.shape)} / tensors on different devices")
     out = torch.empty((B, CO, Y, X), dtype=torch.float32, device=f.device)

@@ -1,5 +1,5 @@
 """DD3D's FCOS heads and post-processing at inference on the device (csrc/dd3d.hip, C ABI pd3_dd3d_head_forward /
-pd3_dd3d_post_process, declared in include/paddle3d_amd_dd3d.h); the arithmetic order and the three definitions (tie
+pd3_dd3d_post_process, declared in include/paddle3d_amd.h); the arithmetic order and the three definitions (tie
 order of the selection, no renormalisation of the egocentric quaternion, the NMS semantics) are stated in that file's
 header and restated in tests/golden/dd3d_numpy.py.
 
@@ -25,7 +25,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._common import check, lib, ptr, stream_ptr, workspace
+from ._common import check, gpu_tensor, lib, nchw_pitch, ptr, stream_ptr, workspace
 
 __all__ = ["dd3d_supported", "dd3d_head_forward", "dd3d_post_process", "flags_of", "MAX_K", "MAX_LEVELS", "ROW",
            "DEFAULTS"]
@@ -55,37 +55,18 @@ def flags_of(cfg):
             8 * bool(cfg["predict_allocentric_rot"]) | 16 * bool(cfg["predict_distance"]))
 
 
-def _gpu(what, t, dev=None, shape=None):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"Unsupported device type for {_OP} operator.")
-    if t.dtype != torch.float32:
-        raise RuntimeError(f"{_OP}: {what} must be torch.float32, got {t.dtype}")
-    if dev is not None and t.device != dev:
-        raise RuntimeError(f"{_OP}: {what} is on {t.device}, expected {dev}")
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise RuntimeError(f"{_OP}: {what} must be {tuple(shape)}, got {tuple(t.shape)}")
-    return t.contiguous()
-
-
 def _pointers(tensors):
     """A host array of device pointers (kept alive by the caller's list of tensors)."""
     return np.ascontiguousarray(np.array([t.data_ptr() for t in tensors], np.uint64))
 
 
 def _strided(what, t, dev, shape):
-    """A [B, C, H, W] view whose rows are contiguous and whose channel planes are H * pitch apart: (tensor, batch
-    stride, pitch), copied to a contiguous tensor when the view is anything else."""
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"Unsupported device type for {_OP} operator.")
+    """nchw_pitch of a checked float32 map of `shape` on `dev`."""
+    gpu_tensor(_OP, what, t, dtype=None, contiguous=False)
     if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or t.device != dev:
         raise RuntimeError(f"{_OP}: {what} must be float32 {tuple(shape)} on {dev}, got {t.dtype} {tuple(t.shape)} on "
                            f"{t.device}")
-    b, c, h, w = t.shape
-    sb, sc, sh, sw = t.stride()
-    if not (sw == 1 and sh >= w and sc == h * sh and sb >= c * sc):
-        t = t.contiguous()
-        sb, sh = c * h * w, w
-    return t, int(sb), int(sh)
+    return nchw_pitch(t)
 
 
 def _config(cfg):
@@ -106,7 +87,7 @@ def _tail(cfg):
 def _dense(logits, centerness, strides):
     if not (len(logits) == len(centerness) == len(strides) >= 1):
         raise RuntimeError(f"{_OP}: one logits map, one centerness map and one stride per level")
-    logits = [_gpu(f"logits[{i}]", t) for i, t in enumerate(logits)]
+    logits = [gpu_tensor(_OP, f"logits[{i}]", t) for i, t in enumerate(logits)]
     dev = logits[0].device
     b, nc = (int(s) for s in logits[0].shape[:2])
     shapes = []
@@ -114,7 +95,8 @@ def _dense(logits, centerness, strides):
         if t.dim() != 4 or tuple(t.shape[:2]) != (b, nc) or t.device != dev:
             raise RuntimeError(f"{_OP}: logits[{i}] must be [{b}, {nc}, H, W] on {dev}, got {tuple(t.shape)}")
         shapes.append((int(t.shape[2]), int(t.shape[3])))
-    centerness = [_gpu(f"centerness[{i}]", t, dev, (b, 1, *shapes[i])) for i, t in enumerate(centerness)]
+    centerness = [gpu_tensor(_OP, f"centerness[{i}]", t, dev=dev, shape=(b, 1, *shapes[i]))
+                  for i, t in enumerate(centerness)]
     return logits, centerness, dev, b, nc, shapes
 
 
@@ -153,9 +135,9 @@ def dd3d_head_forward(logits, centerness, box2d_feat, box3d_feat, strides, box2d
             f3d.append(t3)
         f2d.append(t2)
         table[i] = (h, w, int(strides[i]), pitch, sb)
-    w2 = _gpu("box2d_weight", box2d_weight, dev, (4, c, 3, 3))
-    b2 = _gpu("box2d_bias", box2d_bias, dev, (4,))
-    sc = _gpu("scales", scales, dev, (levels, 6))
+    w2 = gpu_tensor(_OP, "box2d_weight", box2d_weight, dev=dev, shape=(4, c, 3, 3))
+    b2 = gpu_tensor(_OP, "box2d_bias", box2d_bias, dev=dev, shape=(4,))
+    sc = gpu_tensor(_OP, "scales", scales, dev=dev, shape=(levels, 6))
     w3 = b3 = K = canon = None
     wl = ncp = 1
     if has3d:
@@ -164,10 +146,10 @@ def dd3d_head_forward(logits, centerness, box2d_feat, box3d_feat, strides, box2d
         if wl not in (1, levels) or rows3 != 11 * ncp or ncp not in (1, nc):
             raise RuntimeError(f"{_OP}: box3d_weight must be [1 | levels, 11 * (1 | nc), C, 3, 3], got "
                                f"{tuple(box3d_weight.shape)}")
-        w3 = _gpu("box3d_weight", box3d_weight, dev, (wl, rows3, c, 3, 3))
-        b3 = _gpu("box3d_bias", box3d_bias, dev, (wl, rows3))
-        K = _gpu("intrinsics", intrinsics, dev, (b, 3, 3))
-        canon = _gpu("canon_box_sizes", canon_box_sizes[:nc], dev, (nc, 3))
+        w3 = gpu_tensor(_OP, "box3d_weight", box3d_weight, dev=dev, shape=(wl, rows3, c, 3, 3))
+        b3 = gpu_tensor(_OP, "box3d_bias", box3d_bias, dev=dev, shape=(wl, rows3))
+        K = gpu_tensor(_OP, "intrinsics", intrinsics, dev=dev, shape=(b, 3, 3))
+        canon = gpu_tensor(_OP, "canon_box_sizes", canon_box_sizes[:nc], dev=dev, shape=(nc, 3))
     L = lib()
     rows, counts, ws = _outputs(L, dev, b, table, nc, cfg)
     arrays = [_pointers(x) for x in (logits, centerness, f2d)] + [_pointers(f3d) if has3d else None]
@@ -188,7 +170,7 @@ def dd3d_post_process(logits, centerness, box2d_reg, box3d, strides, intrinsics,
     levels = len(shapes)
     if not dd3d_supported(shapes, nc, int(cfg["pre_nms_topk"]), cfg["nms_thresh"]):
         return None
-    reg = [_gpu(f"box2d_reg[{i}]", t, dev, (b, 4, *shapes[i])) for i, t in enumerate(box2d_reg)]
+    reg = [gpu_tensor(_OP, f"box2d_reg[{i}]", t, dev=dev, shape=(b, 4, *shapes[i])) for i, t in enumerate(box2d_reg)]
     table = np.zeros((levels, 5), np.int64)
     for i, (h, w) in enumerate(shapes):
         table[i] = (h, w, int(strides[i]), w, 0)
@@ -197,10 +179,11 @@ def dd3d_post_process(logits, centerness, box2d_reg, box3d, strides, intrinsics,
         ncp = int(box3d[2][0].shape[1])
         if ncp not in (1, nc):
             raise RuntimeError(f"{_OP}: the 3D maps must have 1 or {nc} class rows, got {ncp}")
-        maps3d = [[_gpu(f"{name}[{i}]", t, dev, (b, k * ncp, *shapes[i])) for i, t in enumerate(m)]
+        maps3d = [[gpu_tensor(_OP, f"{name}[{i}]", t, dev=dev, shape=(b, k * ncp, *shapes[i]))
+                   for i, t in enumerate(m)]
                   for name, k, m in zip(("quat", "ctr", "depth", "size", "conf"), (4, 2, 1, 3, 1), box3d)]
-        K = _gpu("intrinsics", intrinsics, dev, (b, 3, 3))
-        canon = _gpu("canon_box_sizes", canon_box_sizes[:nc], dev, (nc, 3))
+        K = gpu_tensor(_OP, "intrinsics", intrinsics, dev=dev, shape=(b, 3, 3))
+        canon = gpu_tensor(_OP, "canon_box_sizes", canon_box_sizes[:nc], dev=dev, shape=(nc, 3))
     L = lib()
     rows, counts, ws = _outputs(L, dev, b, table, nc, cfg)
     arrays = [_pointers(x) for x in (logits, centerness, reg)] + [None if m is None else _pointers(m) for m in maps3d]

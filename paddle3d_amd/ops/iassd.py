@@ -20,7 +20,7 @@ from __future__ import annotations
 
 import torch
 
-from ._common import check, lib, ptr, stream_ptr
+from ._common import check, gpu_tensor, lib, ptr, stream_ptr
 
 __all__ = ["sa_msg_pool_supported", "sa_msg_pool", "iassd_decode"]
 
@@ -28,16 +28,8 @@ MAX_WIDTH = 256
 MAX_NSAMPLE = 64
 
 
-def _gpu(t, op, what, dtype=torch.float32):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"Unsupported device type for {op} operator.")
-    if t.dtype != dtype:
-        raise RuntimeError(f"{op}: {what} must be {dtype}, got {t.dtype}")
-    return t
-
-
 def _shaped(t, op, what, shape):
-    _gpu(t, op, what)
+    gpu_tensor(op, what, t, contiguous=False)
     if t.dim() != len(shape) or any(s is not None and int(d) != s for d, s in zip(t.shape, shape)):
         raise RuntimeError(f"{op}: {what} must be {list(shape)}, got {tuple(t.shape)}")
     return t.contiguous()
@@ -87,7 +79,7 @@ def sa_msg_pool(new_xyz, xyz, features_in, w_pos, scale1, shift1, w2, scale2, sh
             raise RuntimeError(f"{op}: a column offset needs out=")
         out = torch.empty((B, M, C3), dtype=torch.float32, device=q.device)
     else:
-        _gpu(out, op, "out")
+        gpu_tensor(op, "out", out, contiguous=False)
         if out.dim() != 3 or tuple(out.shape[:2]) != (B, M) or not out.is_contiguous():
             raise RuntimeError(f"{op}: out must be a contiguous [{B}, {M}, C], got {tuple(out.shape)}")
         if col < 0 or col + C3 > int(out.shape[2]):
@@ -111,7 +103,7 @@ def iassd_decode(cls_preds, box_preds, centers, mean_size, bins):
     if K < 1:
         raise RuntimeError(f"{op}: cls_preds {tuple(cl.shape)} has no class")
     bx = _shaped(box_preds, op, "box_preds", (M, 6 + 2 * bins))
-    _gpu(centers, op, "centers")
+    gpu_tensor(op, "centers", centers, contiguous=False)
     if centers.dim() != 2 or tuple(centers.shape) != (M, 3):
         raise RuntimeError(f"{op}: centers must be [{M}, 3], got {tuple(centers.shape)}")
     if M > 1 and (centers.stride(1) != 1 or centers.stride(0) < 3):

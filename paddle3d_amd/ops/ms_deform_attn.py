@@ -18,18 +18,12 @@ from __future__ import annotations
 
 import torch
 
-from ._common import check, lib, ptr, stream_ptr
+from ._common import check, gpu_tensor, lib, ptr, stream_ptr
 
 __all__ = ["ms_deform_attn", "ms_deform_attn_backward", "MSDeformAttnFunction"]
 
 _OP = "ms_deform_attn"
 _DTYPES = {torch.float32: 0, torch.float64: 1}
-
-
-def _gpu(t):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"Unsupported device type for {_OP} operator.")
-    return t
 
 
 def _check(value, sampling_locations, attention_weights, spatial_shapes, level_start_index, im2col_step,
@@ -40,7 +34,7 @@ def _check(value, sampling_locations, attention_weights, spatial_shapes, level_s
     if grad_out is not None:
         named.append(("grad_out", grad_out))
     for what, t in named:
-        _gpu(t)
+        gpu_tensor(_OP, what, t, dtype=None, contiguous=False)
     dt = value.dtype
     if dt not in _DTYPES:
         raise RuntimeError(f"{_OP}: value must be float32 or float64, got {dt}")
@@ -135,6 +129,6 @@ class MSDeformAttnFunction(torch.autograd.Function):
 def ms_deform_attn(value, sampling_locations, attention_weights, spatial_shapes, level_start_index, im2col_step):
     """out [B, Q, M*C] (the reference's op; differentiable in value, sampling_locations and attention_weights)."""
     for t in (value, sampling_locations, attention_weights, spatial_shapes, level_start_index):
-        _gpu(t)
+        gpu_tensor(_OP, None, t, dtype=None, contiguous=False)  # the device check alone
     return MSDeformAttnFunction.apply(value, sampling_locations, attention_weights, spatial_shapes,
                                       level_start_index, im2col_step)

@@ -21,23 +21,13 @@ import math
 
 import torch
 
-from ._common import check, host_f32, lib, ptr, stream_ptr
+from ._common import check, gpu_tensor, host_f32, lib, ptr, stream_ptr
 
 __all__ = ["multihead_attention_stream", "petr_coords3d", "mha_stream_supported", "coords3d_supported", "MAX_HEAD_DIM"]
 
 _OP = "petr"
 MAX_HEAD_DIM = 128
 _UNSUPPORTED = -3
-
-
-def _gpu(what, t, dtype, dev=None):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"Unsupported device type for {_OP} operator.")
-    if t.dtype != dtype:
-        raise RuntimeError(f"{_OP}: {what} must be {dtype}, got {t.dtype}")
-    if dev is not None and t.device != dev:
-        raise RuntimeError(f"{_OP}: {what} is on {t.device}, expected {dev}")
-    return t.contiguous()
 
 
 def _mask_u8(what, t, dev):
@@ -62,10 +52,10 @@ def coords3d_supported(num_views, feat_h, feat_w, depth_num=None):
 
 
 def multihead_attention_stream(q, k, v, num_heads, key_padding_mask=None):
-    q = _gpu("q", q, torch.float32)
+    q = gpu_tensor(_OP, "q", q, torch.float32)
     dev = q.device
-    k = _gpu("k", k, torch.float32, dev)
-    v = _gpu("v", v, torch.float32, dev)
+    k = gpu_tensor(_OP, "k", k, torch.float32, dev)
+    v = gpu_tensor(_OP, "v", v, torch.float32, dev)
     M = int(num_heads)
     if q.dim() != 3 or k.dim() != 3 or tuple(v.shape) != tuple(k.shape) or k.shape[0] != q.shape[0] or \
             k.shape[2] != q.shape[2]:
@@ -94,7 +84,7 @@ def multihead_attention_stream(q, k, v, num_heads, key_padding_mask=None):
 
 def petr_coords3d(img2lidars, feat_hw, pad_hw, depth_num, depth_start, position_range, LID, token_mask=None,
                   want_mask=False):
-    m = _gpu("img2lidars", img2lidars, torch.float32)
+    m = gpu_tensor(_OP, "img2lidars", img2lidars, torch.float32)
     dev = m.device
     if m.dim() not in (3, 4) or tuple(m.shape[-2:]) != (4, 4):
         raise RuntimeError(f"{_OP}: img2lidars must be [B, N, 4, 4] or [BN, 4, 4], got {tuple(m.shape)}")

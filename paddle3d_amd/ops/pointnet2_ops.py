@@ -35,20 +35,12 @@ from __future__ import annotations
 
 import torch
 
-from ._common import check, lib, ptr, stream_ptr, workspace
+from ._common import check, gpu_tensor, lib, ptr, stream_ptr, workspace
 
 __all__ = ["farthest_point_sample", "gather_operation", "ball_query_batch", "grouping_operation_batch",
            "gather_operation_grad", "grouping_operation_batch_grad", "GatherOperation", "GroupingOperationBatch",
            "ball_query_stack", "voxel_query_wrapper", "grouping_operation_stack", "grouping_operation_stack_grad",
            "GroupingOperationStack"]
-
-
-def _gpu(t, op, what, dtype):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"Unsupported device type for {op} operator.")
-    if t.dtype != dtype:
-        raise RuntimeError(f"{op}: {what} must be {dtype}, got {t.dtype}")
-    return t
 
 
 def _same_device(op, *ts):
@@ -59,7 +51,7 @@ def _same_device(op, *ts):
 
 
 def _xyz(t, op, what):
-    _gpu(t, op, what, torch.float32)
+    gpu_tensor(op, what, t, torch.float32, contiguous=False)
     if t.dim() != 3 or int(t.shape[2]) != 3:
         raise RuntimeError(f"{op}: {what} must be [B, N, 3], got {tuple(t.shape)}")
     return t.contiguous()
@@ -85,7 +77,7 @@ def farthest_point_sample(points, npoints, tier: int = 0):
 
 
 def _features(points, op):
-    _gpu(points, op, "points", torch.float32)
+    gpu_tensor(op, "points", points, torch.float32, contiguous=False)
     if points.dim() != 3:
         raise RuntimeError(f"{op}: points must be [B, C, N], got {tuple(points.shape)}")
     return points.contiguous()
@@ -94,7 +86,7 @@ def _features(points, op):
 def _gather_fwd(points, idx):
     op = "gather_operation"
     pts = _features(points, op)
-    _gpu(idx, op, "idx", torch.int32)
+    gpu_tensor(op, "idx", idx, torch.int32, contiguous=False)
     _same_device(op, pts, idx)
     B, C, N = (int(s) for s in pts.shape)
     if idx.dim() != 2 or int(idx.shape[0]) != B:
@@ -110,7 +102,7 @@ def gather_operation_grad(grad_out, idx, n):
     """The grad op (gather_points.cc:108-110): grad_out [B, C, M], idx [B, M] -> grad_points [B, C, n]."""
     op = "gather_operation_grad"
     go = _features(grad_out, op)
-    _gpu(idx, op, "idx", torch.int32)
+    gpu_tensor(op, "idx", idx, torch.int32, contiguous=False)
     _same_device(op, go, idx)
     B, C, M = (int(s) for s in go.shape)
     if tuple(idx.shape) != (B, M):
@@ -124,7 +116,7 @@ def gather_operation_grad(grad_out, idx, n):
 def _group_fwd(points, idx):
     op = "grouping_operation_batch"
     pts = _features(points, op)
-    _gpu(idx, op, "idx", torch.int32)
+    gpu_tensor(op, "idx", idx, torch.int32, contiguous=False)
     _same_device(op, pts, idx)
     B, C, N = (int(s) for s in pts.shape)
     if idx.dim() != 3 or int(idx.shape[0]) != B:
@@ -139,11 +131,11 @@ def _group_fwd(points, idx):
 def grouping_operation_batch_grad(grad_out, idx, n):
     """The grad op (group_points_batch.cc:103-106): grad_out [B, C, P, S], idx [B, P, S] -> grad_points [B, C, n]."""
     op = "grouping_operation_batch_grad"
-    _gpu(grad_out, op, "grad_out", torch.float32)
+    gpu_tensor(op, "grad_out", grad_out, torch.float32, contiguous=False)
     if grad_out.dim() != 4:
         raise RuntimeError(f"{op}: grad_out must be [B, C, npoints, nsample], got {tuple(grad_out.shape)}")
     go = grad_out.contiguous()
-    _gpu(idx, op, "idx", torch.int32)
+    gpu_tensor(op, "idx", idx, torch.int32, contiguous=False)
     _same_device(op, go, idx)
     B, C, P, S = (int(s) for s in go.shape)
     if tuple(idx.shape) != (B, P, S):
@@ -186,14 +178,14 @@ class GroupingOperationBatch(torch.autograd.Function):
 def gather_operation(points, idx):
     """[B, C, M] = points[b, c, idx[b, m]] (differentiable in points)."""
     _features(points, "gather_operation")
-    _gpu(idx, "gather_operation", "idx", torch.int32)
+    gpu_tensor("gather_operation", "idx", idx, torch.int32, contiguous=False)
     return GatherOperation.apply(points, idx)
 
 
 def grouping_operation_batch(points, idx):
     """[B, C, npoints, nsample] = points[b, c, idx[b, p, s]] (differentiable in points)."""
     _features(points, "grouping_operation_batch")
-    _gpu(idx, "grouping_operation_batch", "idx", torch.int32)
+    gpu_tensor("grouping_operation_batch", "idx", idx, torch.int32, contiguous=False)
     return GroupingOperationBatch.apply(points, idx)
 
 
@@ -218,14 +210,14 @@ def ball_query_batch(new_xyz, xyz, radius, nsample):
 
 # ---- stack ops ------------------------------------------------------------------------------------------------------
 def _rows(t, op, what, width, dtype=torch.float32):
-    _gpu(t, op, what, dtype)
+    gpu_tensor(op, what, t, dtype, contiguous=False)
     if t.dim() != 2 or (width is not None and int(t.shape[1]) != width):
         raise RuntimeError(f"{op}: {what} must be [rows, {width if width is not None else 'C'}], got {tuple(t.shape)}")
     return t.contiguous()
 
 
 def _counts(t, op, what):
-    _gpu(t, op, what, torch.int32)
+    gpu_tensor(op, what, t, torch.int32, contiguous=False)
     if t.dim() != 1:
         raise RuntimeError(f"{op}: {what} must be [B], got {tuple(t.shape)}")
     return t.contiguous()
@@ -273,7 +265,7 @@ def voxel_query_wrapper(new_xyz, xyz, new_coords, point_indices, radius, nsample
     q = _rows(new_xyz, op, "new_xyz", 3)
     p = _rows(xyz, op, "xyz", 3)
     co = _rows(new_coords, op, "new_coords", 4, torch.int32)
-    _gpu(point_indices, op, "point_indices", torch.int32)
+    gpu_tensor(op, "point_indices", point_indices, torch.int32, contiguous=False)
     if point_indices.dim() != 4:
         raise RuntimeError(f"{op}: point_indices must be [B, Z, Y, X], got {tuple(point_indices.shape)}")
     pi = point_indices.contiguous()
@@ -315,7 +307,7 @@ def _group_stack_fwd(features, features_batch_cnt, idx, idx_batch_cnt):
 def grouping_operation_stack_grad(grad_out, features_batch_cnt, idx, idx_batch_cnt, n):
     """The grad op (group_points_stack.cc:126-130): grad_out [M, C, nsample] -> grad_features [n, C]."""
     op = "grouping_operation_stack_grad"
-    _gpu(grad_out, op, "grad_out", torch.float32)
+    gpu_tensor(op, "grad_out", grad_out, torch.float32, contiguous=False)
     if grad_out.dim() != 3:
         raise RuntimeError(f"{op}: grad_out must be [M, C, nsample], got {tuple(grad_out.shape)}")
     go = grad_out.contiguous()
@@ -353,5 +345,5 @@ def grouping_operation_stack(features, features_batch_cnt, idx, idx_batch_cnt):
     """[M, C, nsample] = features[start(frame(m)) + idx[m, s], c] (differentiable in features)."""
     op = "grouping_operation_stack"
     _rows(features, op, "features", None)
-    _gpu(idx, op, "idx", torch.int32)
+    gpu_tensor(op, "idx", idx, torch.int32, contiguous=False)
     return GroupingOperationStack.apply(features, features_batch_cnt, idx, idx_batch_cnt)

@@ -18,28 +18,13 @@ from __future__ import annotations
 
 import torch
 
-from ._common import check, lib, ptr, stream_ptr
+from ._common import check, gpu_rows, gpu_tensor, lib, ptr, stream_ptr
 
 __all__ = ["stack_sa_pool_supported", "stack_sa_pool", "bev_interpolate"]
 
 
-def _gpu(t, op, what, dtype=torch.float32):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"Unsupported device type for {op} operator.")
-    if t.dtype != dtype:
-        raise RuntimeError(f"{op}: {what} must be {dtype}, got {t.dtype}")
-    return t
-
-
-def _rows(t, op, what, width, dtype=torch.float32):
-    _gpu(t, op, what, dtype)
-    if t.dim() != 2 or (width is not None and int(t.shape[1]) != width):
-        raise RuntimeError(f"{op}: {what} must be [rows, {width if width is not None else 'C'}], got {tuple(t.shape)}")
-    return t.contiguous()
-
-
 def _vec(t, op, what, n, dtype=torch.float32):
-    _gpu(t, op, what, dtype)
+    gpu_tensor(op, what, t, dtype, contiguous=False)
     if tuple(t.shape) != (n,):
         raise RuntimeError(f"{op}: {what} must be [{n}], got {tuple(t.shape)}")
     return t.contiguous()
@@ -59,22 +44,22 @@ def stack_sa_pool_supported(c1, c2, nsample):
 def stack_sa_pool(new_xyz, new_xyz_batch_cnt, xyz, xyz_batch_cnt, features_in, w_pos, scale1, shift1, w2, scale2,
                   shift2, radius, nsample):
     op = "stack_sa_pool"
-    q = _rows(new_xyz, op, "new_xyz", 3)
-    p = _rows(xyz, op, "xyz", 3)
-    w = _rows(w_pos, op, "w_pos", 3)
-    v = _rows(w2, op, "w2", None)
+    q = gpu_rows(op, "new_xyz", new_xyz, 3)
+    p = gpu_rows(op, "xyz", xyz, 3)
+    w = gpu_rows(op, "w_pos", w_pos, 3)
+    v = gpu_rows(op, "w2", w2, None)
     M, N, C1, C2 = int(q.shape[0]), int(p.shape[0]), int(w.shape[0]), int(v.shape[0])
     if int(v.shape[1]) != C1:
         raise RuntimeError(f"{op}: w2 {tuple(v.shape)} for {C1} channels of w_pos")
     f = None
     if features_in is not None:
-        f = _rows(features_in, op, "features_in", C1)
+        f = gpu_rows(op, "features_in", features_in, C1)
         if int(f.shape[0]) != N:
             raise RuntimeError(f"{op}: features_in has {int(f.shape[0])} rows, xyz {N}")
     sc1, sh1 = _vec(scale1, op, "scale1", C1), _vec(shift1, op, "shift1", C1)
     sc2, sh2 = _vec(scale2, op, "scale2", C2), _vec(shift2, op, "shift2", C2)
-    _gpu(new_xyz_batch_cnt, op, "new_xyz_batch_cnt", torch.int32)
-    _gpu(xyz_batch_cnt, op, "xyz_batch_cnt", torch.int32)
+    gpu_tensor(op, "new_xyz_batch_cnt", new_xyz_batch_cnt, torch.int32, contiguous=False)
+    gpu_tensor(op, "xyz_batch_cnt", xyz_batch_cnt, torch.int32, contiguous=False)
     qc, pc = new_xyz_batch_cnt.contiguous(), xyz_batch_cnt.contiguous()
     if qc.dim() != 1 or qc.shape != pc.shape:
         raise RuntimeError(f"{op}: batch counts {tuple(qc.shape)} and {tuple(pc.shape)}")
@@ -93,8 +78,8 @@ def stack_sa_pool(new_xyz, new_xyz_batch_cnt, xyz, xyz_batch_cnt, features_in, w
 
 def bev_interpolate(keypoints, bev, point_cloud_range, voxel_size, bev_stride):
     op = "bev_interpolate"
-    kp = _rows(keypoints, op, "keypoints", 4)
-    _gpu(bev, op, "bev")
+    kp = gpu_rows(op, "keypoints", keypoints, 4)
+    gpu_tensor(op, "bev", bev, contiguous=False)
     if bev.dim() != 4:
         raise RuntimeError(f"{op}: bev must be [B, C, H, W], got {tuple(bev.shape)}")
     im = bev.contiguous()

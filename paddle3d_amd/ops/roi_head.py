@@ -23,26 +23,11 @@ import math
 
 import torch
 
-from ._common import check, host_f32, host_i32, lib, ptr, stream_ptr, workspace
+from ._common import check, gpu_rows, gpu_tensor, host_f32, host_i32, lib, ptr, stream_ptr, workspace
 
 __all__ = ["voxel_pool_supported", "voxel_pool", "roi_grid_points", "rcnn_decode_boxes", "class_agnostic_nms"]
 
 POOLS = {"max_pool": 0, "avg_pool": 1}
-
-
-def _gpu(t, op, what, dtype=torch.float32):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"Unsupported device type for {op} operator.")
-    if t.dtype != dtype:
-        raise RuntimeError(f"{op}: {what} must be {dtype}, got {t.dtype}")
-    return t
-
-
-def _rows(t, op, what, width, dtype=torch.float32):
-    _gpu(t, op, what, dtype)
-    if t.dim() != 2 or (width is not None and int(t.shape[1]) != width):
-        raise RuntimeError(f"{op}: {what} must be [rows, {width if width is not None else 'C'}], got {tuple(t.shape)}")
-    return t.contiguous()
 
 
 def _same_device(op, *ts):
@@ -61,11 +46,11 @@ def voxel_pool(new_xyz, new_coords, xyz, point_indices, features_in, w_pos, pos_
     op = "voxel_pool"
     if pool_method not in POOLS:
         raise NotImplementedError(pool_method)
-    q = _rows(new_xyz, op, "new_xyz", 3)
-    co = _rows(new_coords, op, "new_coords", 4, torch.int32)
-    p = _rows(xyz, op, "xyz", 3)
-    f = _rows(features_in, op, "features_in", None)
-    _gpu(point_indices, op, "point_indices", torch.int32)
+    q = gpu_rows(op, "new_xyz", new_xyz, 3)
+    co = gpu_rows(op, "new_coords", new_coords, 4, torch.int32)
+    p = gpu_rows(op, "xyz", xyz, 3)
+    f = gpu_rows(op, "features_in", features_in, None)
+    gpu_tensor(op, "point_indices", point_indices, torch.int32, contiguous=False)
     if point_indices.dim() != 4:
         raise RuntimeError(f"{op}: point_indices must be [B, Z, Y, X], got {tuple(point_indices.shape)}")
     pi = point_indices.contiguous()
@@ -74,8 +59,8 @@ def voxel_pool(new_xyz, new_coords, xyz, point_indices, features_in, w_pos, pos_
         raise RuntimeError(f"{op}: new_coords has {int(co.shape[0])} rows, new_xyz {M}")
     if int(f.shape[0]) != N:
         raise RuntimeError(f"{op}: features_in has {int(f.shape[0])} rows, xyz {N}")
-    w = _rows(w_pos, op, "w_pos", 3)
-    sc, sh = _gpu(pos_scale, op, "pos_scale").contiguous(), _gpu(pos_shift, op, "pos_shift").contiguous()
+    w = gpu_rows(op, "w_pos", w_pos, 3)
+    sc, sh = gpu_tensor(op, "pos_scale", pos_scale), gpu_tensor(op, "pos_shift", pos_shift)
     if int(w.shape[0]) != C1 or tuple(sc.shape) != (C1,) or tuple(sh.shape) != (C1,):
         raise RuntimeError(f"{op}: w_pos {tuple(w.shape)}, pos_scale {tuple(sc.shape)}, pos_shift {tuple(sh.shape)} "
                            f"for {C1} channels")
@@ -96,7 +81,7 @@ def voxel_pool(new_xyz, new_coords, xyz, point_indices, features_in, w_pos, pos_
 
 def roi_grid_points(rois, grid_size, point_cloud_range, voxel_size, strides):
     op = "roi_grid_points"
-    _gpu(rois, op, "rois")
+    gpu_tensor(op, "rois", rois, contiguous=False)
     if rois.dim() != 3 or int(rois.shape[2]) != 7:
         raise RuntimeError(f"{op}: rois must be [B, R, 7], got {tuple(rois.shape)}")
     r = rois.contiguous()
@@ -117,8 +102,8 @@ def roi_grid_points(rois, grid_size, point_cloud_range, voxel_size, strides):
 
 def rcnn_decode_boxes(rois, box_preds):
     op = "rcnn_decode_boxes"
-    _gpu(rois, op, "rois")
-    _gpu(box_preds, op, "box_preds")
+    gpu_tensor(op, "rois", rois, contiguous=False)
+    gpu_tensor(op, "box_preds", box_preds, contiguous=False)
     if rois.dim() != 3 or int(rois.shape[2]) != 7:
         raise RuntimeError(f"{op}: rois must be [B, R, 7], got {tuple(rois.shape)}")
     n = int(rois.shape[0]) * int(rois.shape[1])
@@ -134,8 +119,8 @@ def rcnn_decode_boxes(rois, box_preds):
 
 def class_agnostic_nms(box_preds, cls_preds, nms_config, score_thresh=None, apply_sigmoid=False, labels=None):
     op = "class_agnostic_nms"
-    _gpu(box_preds, op, "box_preds")
-    _gpu(cls_preds, op, "cls_preds")
+    gpu_tensor(op, "box_preds", box_preds, contiguous=False)
+    gpu_tensor(op, "cls_preds", cls_preds, contiguous=False)
     if box_preds.dim() != 3 or int(box_preds.shape[2]) != 7:
         raise RuntimeError(f"{op}: box_preds must be [B, A, 7], got {tuple(box_preds.shape)}")
     if cls_preds.dim() != 3 or tuple(cls_preds.shape[:2]) != tuple(box_preds.shape[:2]) or int(cls_preds.shape[2]) < 1:
@@ -144,7 +129,7 @@ def class_agnostic_nms(box_preds, cls_preds, nms_config, score_thresh=None, appl
     B, A, K = (int(s) for s in cl.shape)
     lb = None
     if labels is not None:
-        _gpu(labels, op, "labels", torch.int64)
+        gpu_tensor(op, "labels", labels, torch.int64, contiguous=False)
         if tuple(labels.shape) != (B, A):
             raise RuntimeError(f"{op}: labels {tuple(labels.shape)} for {B} x {A} boxes")
         lb = labels.contiguous()

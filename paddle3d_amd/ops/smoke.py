@@ -27,7 +27,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._common import check, lib, ptr, stream_ptr, workspace
+from ._common import check, gpu_tensor, lib, nchw_pitch, ptr, stream_ptr, workspace
 
 __all__ = ["smoke_supported", "smoke_head_forward", "smoke_post_process", "group_norm_tables", "batch_norm_tables",
            "REG_CHANNELS", "MAX_K", "FORWARD", "EXPORT"]
@@ -67,27 +67,16 @@ def batch_norm_tables(running_mean, running_var, batch, eps=1e-5):
     return t[None].expand(int(batch), 2, t.shape[1]).contiguous()
 
 
-def _gpu(what, t, dev=None, shape=None):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"Unsupported device type for {_OP} operator.")
-    if t.dtype != torch.float32:
-        raise RuntimeError(f"{_OP}: {what} must be torch.float32, got {t.dtype}")
-    if dev is not None and t.device != dev:
-        raise RuntimeError(f"{_OP}: {what} is on {t.device}, expected {dev}")
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise RuntimeError(f"{_OP}: {what} must be {tuple(shape)}, got {tuple(t.shape)}")
-    return t.contiguous()
-
-
 def _camera(Ks, trans, image_size, depth_ref, dim_ref, b, nc, mode, dev):
-    Ks = _gpu("Ks", Ks, dev, (b, 3, 3))
+    Ks = gpu_tensor(_OP, "Ks", Ks, dev=dev, shape=(b, 3, 3))
     if mode == FORWARD:
-        trans = _gpu("trans_mat", trans, dev, (b, 3, 3))
-        image_size = _gpu("image_size", image_size.reshape(-1)[:2], dev, (2,))
+        trans = gpu_tensor(_OP, "trans_mat", trans, dev=dev, shape=(b, 3, 3))
+        image_size = gpu_tensor(_OP, "image_size", image_size.reshape(-1)[:2], dev=dev, shape=(2,))
     else:
-        trans = _gpu("down_ratios", trans.reshape(-1)[:2], dev, (2,))
+        trans = gpu_tensor(_OP, "down_ratios", trans.reshape(-1)[:2], dev=dev, shape=(2,))
         image_size = None
-    return (Ks, trans, image_size, _gpu("depth_ref", depth_ref, dev, (2,)), _gpu("dim_ref", dim_ref, dev, (nc, 3)))
+    return (Ks, trans, image_size, gpu_tensor(_OP, "depth_ref", depth_ref, dev=dev, shape=(2,)),
+            gpu_tensor(_OP, "dim_ref", dim_ref, dev=dev, shape=(nc, 3)))
 
 
 def _tail(reg_channels, max_detection, det_threshold, mode, pred_2d):
@@ -96,20 +85,13 @@ def _tail(reg_channels, max_detection, det_threshold, mode, pred_2d):
 
 
 def _strided(what, t, dev):
-    """A [B, C, H, W] view whose rows are contiguous and whose channel planes are H * pitch apart: (tensor, batch
-    stride, pitch), copied to a contiguous tensor when the view is anything else."""
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"Unsupported device type for {_OP} operator.")
+    """nchw_pitch of a checked float32 [B, C, H, W] map."""
+    gpu_tensor(_OP, what, t, dtype=None, contiguous=False)
     if t.dtype != torch.float32 or t.dim() != 4:
         raise RuntimeError(f"{_OP}: {what} must be float32 [B, C, H, W], got {t.dtype} {tuple(t.shape)}")
     if dev is not None and t.device != dev:
         raise RuntimeError(f"{_OP}: {what} is on {t.device}, expected {dev}")
-    b, c, h, w = t.shape
-    sb, sc, sh, sw = t.stride()
-    if not (sw == 1 and sh >= w and sc == h * sh and sb >= c * sc):
-        t = t.contiguous()
-        sb, sh = c * h * w, w
-    return t, int(sb), int(sh)
+    return nchw_pitch(t)
 
 
 def smoke_head_forward(cls_feat, reg_feat, cls_norm, reg_norm, cls_weight, cls_bias, reg_weight, reg_bias, Ks, trans,
@@ -130,13 +112,14 @@ def smoke_head_forward(cls_feat, reg_feat, cls_norm, reg_norm, cls_weight, cls_b
     nc, g = int(cls_weight.shape[0]), int(groups)
     if not smoke_supported(c, g, nc, h, w, int(max_detection), reg_channels, pred_2d):
         return None
-    cw = _gpu("cls_weight", cls_weight.reshape(nc, -1), dev, (nc, c))
-    cb = _gpu("cls_bias", cls_bias, dev, (nc,))
-    rw = _gpu("reg_weight", reg_weight.reshape(reg_weight.shape[0], -1), dev, (10, c))
-    rbias = _gpu("reg_bias", reg_bias, dev, (10,))
-    norms = [_gpu(n, t, dev, (c,)) for n, t in zip(("cls_gamma", "cls_beta", "reg_gamma", "reg_beta"),
-                                                  (*cls_norm, *reg_norm))]
-    tabs = [None if t is None else _gpu("tables", t, dev, (b, 2, g)) for t in (cls_tables, reg_tables)]
+    cw = gpu_tensor(_OP, "cls_weight", cls_weight.reshape(nc, -1), dev=dev, shape=(nc, c))
+    cb = gpu_tensor(_OP, "cls_bias", cls_bias, dev=dev, shape=(nc,))
+    rw = gpu_tensor(_OP, "reg_weight", reg_weight.reshape(reg_weight.shape[0], -1), dev=dev, shape=(10, c))
+    rbias = gpu_tensor(_OP, "reg_bias", reg_bias, dev=dev, shape=(10,))
+    norms = [gpu_tensor(_OP, n, t, dev=dev, shape=(c,))
+             for n, t in zip(("cls_gamma", "cls_beta", "reg_gamma", "reg_beta"), (*cls_norm, *reg_norm))]
+    tabs = [None if t is None else gpu_tensor(_OP, "tables", t, dev=dev, shape=(b, 2, g))
+            for t in (cls_tables, reg_tables)]
     cam = _camera(Ks, trans, image_size, depth_ref, dim_ref, b, nc, mode, dev)
     L = lib()
     rows = torch.empty((b, int(max_detection), 14), dtype=torch.float32, device=dev)
@@ -157,14 +140,14 @@ def smoke_post_process(heat, regression, Ks, trans, image_size, depth_ref, dim_r
                        mode=FORWARD, reg_channels=REG_CHANNELS, pred_2d=True):
     """heat [B, nc, H, W] (the clipped sigmoid heat map), regression [B, 10, H, W] (activations applied):
     SMOKEPredictor's outputs."""
-    heat = _gpu("heat", heat)
+    heat = gpu_tensor(_OP, "heat", heat)
     dev = heat.device
     if heat.dim() != 4:
         raise RuntimeError(f"{_OP}: heat must be [B, nc, H, W], got {tuple(heat.shape)}")
     b, nc, h, w = (int(s) for s in heat.shape)
     if not smoke_supported(None, None, nc, h, w, int(max_detection), reg_channels, pred_2d):
         return None
-    regression = _gpu("regression", regression, dev, (b, 10, h, w))
+    regression = gpu_tensor(_OP, "regression", regression, dev=dev, shape=(b, 10, h, w))
     cam = _camera(Ks, trans, image_size, depth_ref, dim_ref, b, nc, mode, dev)
     L = lib()
     rows = torch.empty((b, int(max_detection), 14), dtype=torch.float32, device=dev)

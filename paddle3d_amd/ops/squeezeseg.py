@@ -28,7 +28,7 @@ import math
 import numpy as np
 import torch
 
-from ._common import check, lib, ptr, stream_ptr
+from ._common import check, gpu_tensor, lib, ptr, stream_ptr
 
 __all__ = ["sac_isk_supported", "fold_batch_norm", "pack_sac_attention_weight", "unpack_sac_attention_weight",
            "pack_sac_mlp_weight", "unpack_sac_mlp_weight", "sac_isk_forward", "range_project", "MAX_CHANNELS",
@@ -41,16 +41,6 @@ _STEPS = 37   # the taps padded to 148, four per MFMA step
 _UNSUPPORTED = -3
 RANGE_MEAN = (12.12, 10.88, 0.23, -1.04, 0.21)  # range, x, y, z, remission (configs/_base_/semantickitti.yml)
 RANGE_STD = (12.32, 11.47, 6.91, 0.86, 0.16)
-
-
-def _gpu(what, t, dtype, dev=None):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"Unsupported device type for {_OP} operator.")
-    if t.dtype != dtype:
-        raise RuntimeError(f"{_OP}: {what} must be {dtype}, got {t.dtype}")
-    if dev is not None and t.device != dev:
-        raise RuntimeError(f"{_OP}: {what} is on {t.device}, expected {dev}")
-    return t.contiguous()
 
 
 def sac_isk_supported(channels, height=1, width=1, batch=1):
@@ -131,9 +121,9 @@ def unpack_sac_mlp_weight(packed, channels):
 
 
 def sac_isk_forward(xyz, feature, attn_packed, attn_scale, attn_shift, mlp_packed, mlp_scale, mlp_shift):
-    xyz = _gpu("xyz", xyz, torch.float32)
+    xyz = gpu_tensor(_OP, "xyz", xyz, torch.float32)
     dev = xyz.device
-    feature = _gpu("feature", feature, torch.float32, dev)
+    feature = gpu_tensor(_OP, "feature", feature, torch.float32, dev)
     if feature.dim() != 4 or xyz.dim() != 4 or xyz.shape[1] != 3 or xyz.shape[0] != feature.shape[0] or \
             tuple(xyz.shape[2:]) != tuple(feature.shape[2:]):
         raise RuntimeError(f"{_OP}: xyz must be [N, 3, H, W] and feature [N, C, H, W], got {tuple(xyz.shape)} and "
@@ -147,7 +137,7 @@ def sac_isk_forward(xyz, feature, attn_packed, attn_scale, attn_shift, mlp_packe
     names = ("attn_packed", "attn_scale", "attn_shift", "mlp_packed", "mlp_scale", "mlp_shift")
     params = []
     for name, t, shape in zip(names, (attn_packed, attn_scale, attn_shift, mlp_packed, mlp_scale, mlp_shift), shapes):
-        t = _gpu(name, t, torch.float32, dev)
+        t = gpu_tensor(_OP, name, t, torch.float32, dev)
         if tuple(t.shape) != shape:
             raise RuntimeError(f"{_OP}: {name} must be {shape}, got {tuple(t.shape)}")
         params.append(t)
@@ -168,9 +158,9 @@ def _host_f64(values, what):
 
 
 def range_project(points, offsets, height=64, width=1024, fov_up=3.0, fov_down=-25.0, mean=RANGE_MEAN, std=RANGE_STD):
-    points = _gpu("points", points, torch.float32)
+    points = gpu_tensor(_OP, "points", points, torch.float32)
     dev = points.device
-    offsets = _gpu("offsets", offsets, torch.int32, dev)
+    offsets = gpu_tensor(_OP, "offsets", offsets, torch.int32, dev)
     if points.dim() != 2 or points.shape[1] != 4 or offsets.dim() != 1 or offsets.numel() < 1:
         raise RuntimeError(f"{_OP}: points must be [P, 4] and offsets [B + 1], got {tuple(points.shape)} and "
                            f"{tuple(offsets.shape)}")

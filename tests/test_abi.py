@@ -57,6 +57,8 @@ BLOCKS = {
                                         "pd3_anchor3d_get_bboxes"},
     "test_pillar_conv_span_gpu": {"pd3_pillar_conv_span_x3"},
     "test_memory_safety_iassd_gpu": {"pd3_sa_msg_pool", "pd3_iassd_decode"},
+    "test_memory_safety_smoke_gpu": {"pd3_smoke_head_workspace", "pd3_smoke_head_forward", "pd3_smoke_post_process"},
+    "test_memory_safety_dd3d_gpu": {"pd3_dd3d_workspace", "pd3_dd3d_head_forward", "pd3_dd3d_post_process"},
 }
 
 
@@ -92,13 +94,17 @@ def test_entry_points_match_the_header(built):
 def test_entry_points_name_the_module_of_their_scenarios():
     from paddle3d_amd import _lib
 
-    assert len(_lib.symbols()) == len(_lib.ENTRY_POINTS) == 132
+    assert len(_lib.symbols()) == len(_lib.ENTRY_POINTS) == 138
     assert list(dict.fromkeys(row[2] for row in _lib.ENTRY_POINTS.values())) == list(BLOCKS)
     for module, want in BLOCKS.items():
         assert os.path.isfile(os.path.join(ROOT, "tests", module + ".py")), module
         names = _lib.symbols(module)
         assert len(names) == want if isinstance(want, int) else set(names) == want, (module, names)
     assert _lib.symbols("test_memory_safety_squeezeseg_gpu") == ("pd3_sac_isk_forward", "pd3_range_project")  # in order
+    assert _lib.symbols("test_memory_safety_smoke_gpu") == ("pd3_smoke_head_workspace", "pd3_smoke_head_forward",
+                                                            "pd3_smoke_post_process")
+    assert _lib.symbols("test_memory_safety_dd3d_gpu") == ("pd3_dd3d_workspace", "pd3_dd3d_head_forward",
+                                                           "pd3_dd3d_post_process")
     assert _lib.symbols("test_no_such_module") == ()
     with pytest.raises(ValueError, match="pd3_version has a row"):  # a second row for a name is refused
         _lib._block("test_memory_safety_roi_gpu", {"pd3_version": (C.c_int, [])})

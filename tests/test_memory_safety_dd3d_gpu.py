@@ -1,4 +1,4 @@
-"""DD3D's entry points (the rows of paddle3d_amd._lib.DD3D_ENTRY_POINTS, which name this module) under guarded allocations:
+"""DD3D's entry points (the rows of paddle3d_amd._lib.ENTRY_POINTS that name this module) under guarded allocations:
 tests/guarded.py's Protocol.  Each scenario builds seeded inputs and returns `(inputs, call)`; it runs plain, guarded
 with fill 0x00 and guarded with fill 0xFF, and the test asserts: no guard band damaged (no store outside an output or
 the workspace), every input bit-equal to its clone, every output bit-equal across the three runs (nothing depends on

@@ -40,7 +40,7 @@ KEY_OUT = 0x3FFFFFFF         # postprocess.hip kKeyOut
 SSD_KEY_OUT = 0x3FFFFFFF     # ssd_head.hip kSsdKeyOut
 BD_KEY_NAN = 0x3FFFFFFF      # bevdet_postprocess.hip kBdKeyNan
 KEY_NAN = 0x3FFFFFFF         # bevformer_decoder.hip kKeyNan
-KEY_ALL = ONE_BITS + 2       # anchor3d_head.hip kKeyAll
+KEY_ALL = ONE_BITS + 2       # block_topk.hpp kScoreKeyAll
 TAKE_ALL = 0xFFFFFFFF        # the probe's skip_cut cut-off; also what it writes for a refused set
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -69,13 +69,13 @@ def source_constants():
         "WAVE": one(cm, r"constexpr int kWave = (\d+);"),
         "Q": one(bt, r"constexpr int kQ = (\d+);"),
         "DIGIT": one(bt, r"const int w = min\(hi, (\d+)\), shift = hi - w;"),
-        "ONE_BITS": one(bt, r"constexpr uint32_t one = (0x[0-9A-Fa-f]+)u;"),
+        "ONE_BITS": one(bt, r"constexpr uint32_t kScoreKeyOne = (0x[0-9A-Fa-f]+)u;"),
         "KEY_OUT": one(pp, r"constexpr uint32_t kKeyOut = (0x[0-9A-Fa-f]+)u;"),
         "SSD_KEY_OUT": one(ssd, r"constexpr uint32_t kSsdKeyOut = (0x[0-9A-Fa-f]+)u;"),
         "BD_KEY_NAN": one(bd, r"constexpr uint32_t kBdKeyNan = (0x[0-9A-Fa-f]+)u;"),
         "KEY_NAN": one(dec, r"constexpr uint32_t kKeyNan = (0x[0-9A-Fa-f]+)u;"),
-        "KEY_ALL": one(a3d, r"constexpr uint32_t kOneBits = (0x[0-9A-Fa-f]+)u;")
-                   + one(a3d, r"constexpr uint32_t kKeyAll = kOneBits \+ (\d+)u;"),
+        "KEY_ALL": one(bt, r"constexpr uint32_t kScoreKeyOne = (0x[0-9A-Fa-f]+)u;")
+                   + one(bt, r"constexpr uint32_t kScoreKeyAll = kScoreKeyOne \+ (\d+)u;"),
         "LDS_MAX_N": one(read("selfcheck.hip"), r"constexpr int kProbeMaxLdsKeys = (\d+);"),
     }
     # the rules that are not a number: the barrier rule of the sort, the histogram's bins and replicas, the partition
@@ -88,7 +88,8 @@ def source_constants():
     assert one(pp, r"constexpr int kTopkMaxHw = (\d+);") == out["LDS_MAX_N"]
     assert "return i + (i >> 4); }  // postprocess.hip kidx" in read("selfcheck.hip")
     assert "__device__ __forceinline__ int kidx(int i) { return i + (i >> 4); }" in pp
-    for text, name in ((bd, "kBdKeyBits"), (dec, "kKeyBits"), (a3d, "kKeyBits")):
+    assert "block_topk_cut(K, kScoreKeyBits, hist, scr, visit) : TopkCut{kScoreKeyAll, 0}" in a3d
+    for text, name in ((bd, "kBdKeyBits"), (dec, "kKeyBits"), (bt, "kScoreKeyBits")):
         assert one(text, rf"constexpr int {name} = (\d+);") == 30
     return out
 
