@@ -25,7 +25,7 @@ three times; the decode reads that map through strided views, without a [B, H, W
 refuses (conv.patch_supported(1, C, rows, H, W): C % 16, H * W % 4) takes the transcription; fused="force" raises
 there instead (and on CPU tensors).  fused=None: FUSED_HEAD_DEFAULT (DESIGN 4.5zd has the measurement behind it).  The
 stacked, packed weight is kept with the signature of the parameters it was made from and rebuilt when that changes
-(centerpoint._InferenceCache: a state-dict load, .to(), train()).
+(derived.py: a state-dict load, .to(), an in-place write, train()).
 
 The decode (ResidualCoder.decode_paddle, utils/box_coder.py:66-100, and the direction fix of anchor_head.py:151-163) is
 elementwise torch on the device, the same statements for both paths.  Nothing in forward synchronises with the host.
@@ -37,7 +37,7 @@ import torch
 from torch import nn
 
 from ._lib import Paddle3DAmdError
-from .centerpoint import _InferenceCache
+from .derived import InferenceCache, derived
 from .ops import conv as _conv
 from .roi_heads import ResidualCoder
 
@@ -92,7 +92,7 @@ class AnchorGenerator:
         return all_anchors, num_anchors_per_location
 
 
-class AnchorHeadSingle(_InferenceCache, nn.Module):
+class AnchorHeadSingle(InferenceCache, nn.Module):
     def __init__(self, model_cfg, input_channels, class_names, voxel_size, point_cloud_range, anchor_generator_cfg,
                  num_dir_bins, anchor_target_cfg=None, predict_boxes_when_training=None, loss_weights=None, fused=None):
         super().__init__()
@@ -168,12 +168,12 @@ class AnchorHeadSingle(_InferenceCache, nn.Module):
 
     def _stacked(self):
         """(packed [rows, C] weight in the 1x1 kernel's operand order, bias [rows]) of cls | box | dir."""
-        if not self._cache_valid():
+        def build():
             convs = (self.conv_cls, self.conv_box, self.conv_dir_cls)
             w = torch.cat([c.weight.detach().float() for c in convs], dim=0)
             b = torch.cat([c.bias.detach().float() for c in convs], dim=0).contiguous()
-            self._store_cache((_conv.pack_patch_weight(w, 1, False), b))
-        return self._cache
+            return _conv.pack_patch_weight(w, 1, False), b
+        return derived(self, "stacked", build)
 
     def _maps(self, x):
         """cls, box, dir predictions as [B, H, W, C'] views."""

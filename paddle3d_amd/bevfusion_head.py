@@ -29,7 +29,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .centerpoint import _InferenceCache
+from .derived import InferenceCache, derived
 from .ops import anchor3d_head as _ops
 from .ops import conv as _conv
 from .ops import iou3d_nms as _nms
@@ -126,7 +126,7 @@ def box3d_multiclass_nms(mlvl_bboxes, mlvl_bboxes_for_nms, mlvl_scores, score_th
     return bboxes, scores, labels, dir_scores
 
 
-class Anchor3DHead(_InferenceCache, nn.Module):
+class Anchor3DHead(InferenceCache, nn.Module):
     def __init__(self, num_classes, in_channels, feat_channels=256, use_direction_classifier=True, anchor_generator=None,
                  assigner_per_size=False, assign_per_class=False, diff_rad_by_sin=True, dir_offset=0, dir_limit_offset=1,
                  bbox_coder=None, loss_cls=None, loss_bbox=None, loss_dir=None, use_sigmoid_cls=True, bbox_assigner=None,
@@ -164,12 +164,12 @@ class Anchor3DHead(_InferenceCache, nn.Module):
 
     # ---- derived tensors ---------------------------------------------------------------------------------------------
     def _plan(self):
-        if not self._cache_valid():
+        def build():
             convs = [self.conv_cls, self.conv_reg] + ([self.conv_dir_cls] if self.use_direction_classifier else [])
-            self._store_cache(dict(
+            return dict(
                 cls_packed=_ops.pack_cls_weight(self.conv_cls.weight.detach(), self.num_classes),
-                patch=[_conv.pack_patch_weight(c.weight.detach(), 1, False) for c in convs]))
-        return self._cache
+                patch=[_conv.pack_patch_weight(c.weight.detach(), 1, False) for c in convs])
+        return derived(self, "plan", build)
 
     def anchors_for(self, featmap_size, device):
         """The level-0 anchor table [H * W * A, code_size] of a map size, built once per (size, device)."""

@@ -32,6 +32,7 @@ import torch
 import torch.nn as nn
 
 from ._lib import Paddle3DAmdError
+from .derived import InferenceCache, derived, invalidate_derived
 from .ops import centerpoint_postprocess as _cp
 from .ops import conv as _conv
 from .ops import pointpillars_scatter as _ps
@@ -102,9 +103,9 @@ class PFNLayer(nn.Module):
         nn.init.uniform_(self.linear.weight, -bound, bound)
 
 
-class PillarFeatureNet(nn.Module):
+class PillarFeatureNet(InferenceCache, nn.Module):
     """pillar_encoder.py:108-210 (legacy=False, with_distance=False).  The folded parameters are rebuilt on
-    every call in training mode and whenever the module is moved / reloaded (see _InferenceCache below)."""
+    every call in training mode and whenever the module is moved / reloaded (derived.py); train() drops them."""
 
     def __init__(self, in_channels=4, feat_channels=(64,), with_distance=False, max_num_points_in_voxel=20,
                  voxel_size=(0.2, 0.2, 4), point_cloud_range=(0, -40, -3, 70.4, 40, 1), legacy=False):
@@ -128,11 +129,9 @@ class PillarFeatureNet(nn.Module):
         vs32, pr32 = np.asarray(voxel_size, np.float32), np.asarray(point_cloud_range, np.float32)
         self.grid_xy = tuple(int(math.floor(float((pr32[3 + a] - pr32[a]) / vs32[a]) + 0.5)) for a in range(2))
         self.max_num_points_in_voxel = max_num_points_in_voxel
-        self._folded = None
 
-    def train(self, mode: bool = True):
-        self._folded = None
-        return super().train(mode)
+    def _weights(self):
+        return self._fold() if self.training else derived(self, "folded", self._fold)
 
     def _fold(self):
         out = []
@@ -144,11 +143,8 @@ class PillarFeatureNet(nn.Module):
 
     def forward(self, features, num_points_per_voxel, coors):
         """features [M,P,D], num_points [M] int32, coors [M,4] int32 -> [M, C]."""
-        sig = _param_signature(self)
-        if self.training or self._folded is None or self._folded[0] != sig:
-            self._folded = (sig, self._fold())
         return _ve.pillar_feature_net(features, num_points_per_voxel, coors, self.vx, self.vy, self.x_offset,
-                                      self.y_offset, *self._folded[1])
+                                      self.y_offset, *self._weights())
 
     def forward_indexed(self, points, vox_span, point_list, coors):
         """forward() reading the pillars' points through the voxelizer's index (HardVoxelizer.index) from the point
@@ -157,11 +153,8 @@ class PillarFeatureNet(nn.Module):
         than 65 536 cells along x or y is answered with None here (the caller runs the pair); no host sync."""
         if len(self.pfn_layers) != 2 or max(self.grid_xy) > _ve.INDEXED_MAX_AXIS_CELLS:
             return None
-        sig = _param_signature(self)
-        if self.training or self._folded is None or self._folded[0] != sig:
-            self._folded = (sig, self._fold())
         return _ve.pillar_feature_net_indexed(points, vox_span, point_list, coors, self.max_num_points_in_voxel,
-                                              self.vx, self.vy, self.x_offset, self.y_offset, *self._folded[1])
+                                              self.vx, self.vy, self.x_offset, self.y_offset, *self._weights())
 
 
 class HardVFE(nn.Module):
@@ -224,67 +217,6 @@ class PointPillarsScatter(nn.Module):
         pillar features itself (SecondBackbone's first convolution): no canvas is written.  The models call this
         when they fuse (`model.scatter`); the module's own forward keeps returning a tensor for everyone else."""
         return _ps.SparseCanvas(voxel_features, coords, batch_size, self.ny, self.nx)
-
-
-def _param_signature(module):
-    """(storage, version, device) of every parameter and buffer below `module`: changes when any of them is
-    reloaded, moved or written in place THROUGH THE TENSOR ITSELF (`load_state_dict` on this module or a child,
-    `.to()`, `with torch.no_grad(): p.mul_(2)`, an optimizer step).  It does NOT see a write through `p.data`
-    (`p.data.copy_(...)`, `p.data.mul_(2)`): `.data` is a detached alias with a version counter of its own, and
-    reading the contents instead would cost a device -> host round trip on every forward.  Code that writes through
-    `.data` (or through a raw pointer) calls `invalidate_derived(model)` afterwards."""
-    return tuple((t.data_ptr(), t._version, str(t.device)) for t in list(module.parameters()) + list(module.buffers()))
-
-
-def invalidate_derived(module):
-    """Drop every weight derived for inference (folded BatchNorm, packed kernel layouts) below `module`; the next
-    forward rebuilds them from the current parameters.  Needed only after a write the signature cannot see
-    (`param.data.*`, see _param_signature); `load_state_dict`, `.to()`, `train()` and in-place tensor ops are
-    detected without it."""
-    for m in module.modules():
-        if hasattr(m, "_drop_cache"):
-            m._drop_cache()
-        if hasattr(m, "_folded"):
-            m._folded = None
-        if getattr(m, "_pd3_folded", None) is not None:
-            object.__setattr__(m, "_pd3_folded", None)
-    return module
-
-
-class _InferenceCache:
-    """Mixin of the parameter-holding layers: weights derived for inference (BatchNorm folded, packed in the
-    kernels' layouts) live in ``self._cache`` together with the signature of the tensors they were derived from
-    and are rebuilt whenever that signature differs (a reload of this module or of a child, ``.to()``, an in-place
-    write) -- checked on every forward, a few microseconds; ``train()`` drops them outright."""
-
-    _cache = None
-    _cache_sig = None
-
-    def _drop_cache(self):
-        self.__dict__["_cache"] = None
-        self.__dict__["_cache_sig"] = None
-
-    def _cache_valid(self):
-        return self._cache is not None and self._cache_sig == _param_signature(self)
-
-    def _store_cache(self, value):
-        self.__dict__["_cache"] = value
-        self.__dict__["_cache_sig"] = _param_signature(self)
-        return value
-
-    def train(self, mode: bool = True):
-        self._drop_cache()
-        return super().train(mode)
-
-    def invalidate(self):
-        """Public form of _drop_cache for this module and everything below it (see invalidate_derived)."""
-        invalidate_derived(self)
-        return self
-
-    def _require_eval(self):
-        if self.training:
-            raise RuntimeError(f"{type(self).__name__}: paddle3d_amd implements the inference path only "
-                               "(BatchNorm folded into the HIP kernels); call .eval() first")
 
 
 def _conv_bn_relu(cin, cout, k, stride=1, padding=0, transpose=False, eps=1e-3, momentum=0.01, bias=False):
@@ -420,7 +352,7 @@ def _fold_conv3x3(conv, bn):
     return _Conv3x3(w, b, conv.stride[0])
 
 
-class SecondBackbone(_InferenceCache, nn.Module):
+class SecondBackbone(InferenceCache, nn.Module):
     """second_backbone.py:72-120 (parameter names blocks.<i>.<j>.* as in the reference).  The modules hold the
     parameters; forward runs every convolution (BatchNorm folded, ReLU fused) on the library's kernels."""
 
@@ -446,13 +378,13 @@ class SecondBackbone(_InferenceCache, nn.Module):
         #                           neck reads that form: no fp32 NCHW copy of a stage is written at all)
 
     def _plan(self):
-        if not self._cache_valid():
+        def build():
             plan = []
             for blk in self.blocks:
                 mods = list(blk)
                 plan.append([_fold_conv3x3(mods[i], mods[i + 1]) for i in range(0, len(mods), 3)])
-            self._store_cache(plan)
-        return self._cache
+            return plan
+        return derived(self, "plan", build)
 
     def forward(self, x):
         """-> the block outputs.  A stage whose width is not a multiple of 4 (CenterPoint-Voxel: 90) comes back in
@@ -552,7 +484,7 @@ class SecondBackbone(_InferenceCache, nn.Module):
         return tuple(outs)
 
 
-class SecondFPN(_InferenceCache, nn.Module):
+class SecondFPN(InferenceCache, nn.Module):
     """second_fpn.py:99-157 (use_spatial_attn_before_concat unsupported: unused on the path).  Every level is a
     kernel = stride convolution / transposed convolution: one patch GEMM each, written straight into its channel
     slice of the concatenated map (no concat pass)."""
@@ -572,7 +504,7 @@ class SecondFPN(_InferenceCache, nn.Module):
         self.deblocks = nn.ModuleList(deblocks)
 
     def _plan(self):
-        if not self._cache_valid():
+        def build():
             plan, off = [], 0
             for blk in self.deblocks:
                 conv, bn = blk[0], blk[1]
@@ -587,14 +519,14 @@ class SecondFPN(_InferenceCache, nn.Module):
                 plan.append(dict(mode=mode, w=_conv.pack_patch_weight(w, mode, tr), wraw=w, tr=tr, b=b, cin=cin, cout=cout, off=off,
                                  scale={0: 0.5, 1: 1, 2: 2, 3: 4}[mode]))
                 off += cout
-            self._store_cache((plan, off))
-        return self._cache
+            return plan, off
+        return derived(self, "plan", build)
 
     # ---- mixed precision (CenterPoint.set_amp): every level as one fp16 gather-GEMM over the pixels ------------------
-    def _amp_level(self, i, p, n, h, w, dev, tag=None):
-        """Static pieces of level i on an [n, h, w, cin] fp16 NHWC input: the neighbour table over the output pixels
-        (a kernel = stride convolution reads s x s input pixels, a transposed one exactly one, at the tap its position
-        selects), its tile order, and the weight as [taps][cin][cout] in the fp16 kernel's operand order."""
+    def _amp_level(self, i, n, h, w, dev):
+        """The pieces of level i on an [n, h, w, cin] fp16 NHWC input that depend on the shape alone: the neighbour
+        table over the output pixels (a kernel = stride convolution reads s x s input pixels, a transposed one exactly
+        one, at the tap its position selects) and its tile order."""
         key = (i, n, h, w, str(dev))  # (per device: a model moved with .to() must not reuse the old device's tables)
         cache = self.__dict__.setdefault("_amp_tables", {})
         if len(cache) > 64:  # (input shapes seen so far: bounded, the tables are rebuilt in a millisecond)
@@ -617,22 +549,27 @@ class SecondFPN(_InferenceCache, nn.Module):
                 nbr = torch.stack(cols, 1).int().contiguous()
             order = _sp3.tile_order(nbr) if tr and s > 1 else None
             cache[key] = (nbr, order, ho, wo)
-        wkey = ("w", i, str(dev))
-        if tag is None:
-            tag = _param_signature(self)
-        if wkey not in cache or cache[wkey][0] != tag:
-            conv, bn = self.deblocks[i][0], self.deblocks[i][1]
-            tr = isinstance(conv, nn.ConvTranspose2d)
-            wf, bf = _fold_conv_bn(conv, bn)
-            # [taps = ky * s + kx][cin][cout]
-            wk = wf.permute(2, 3, 0, 1) if tr else wf.permute(2, 3, 1, 0)
-            wk = wk.reshape(-1, wk.shape[2], wk.shape[3]).contiguous()
-            parts = []
-            step = 128 if wk.shape[2] % 128 == 0 else (64 if wk.shape[2] % 64 == 0 else 32)
-            for c0 in range(0, wk.shape[2], step):
-                parts.append((c0, step, _sp3.pack_weight_f16(wk[:, :, c0:c0 + step].contiguous()), bf[c0:c0 + step].contiguous()))
-            cache[wkey] = (tag, parts)
-        return cache[key], cache[wkey][1]
+        return cache[key]
+
+    def _amp_weights(self):
+        """Per level, the folded weight as [taps][cin][cout] in the fp16 kernel's operand order, in slices of output
+        channels: one slot for all levels, so a forward takes one signature and not one per level."""
+        def build():
+            levels = []
+            for blk in self.deblocks:
+                conv, bn = blk[0], blk[1]
+                tr = isinstance(conv, nn.ConvTranspose2d)
+                wf, bf = _fold_conv_bn(conv, bn)
+                # [taps = ky * s + kx][cin][cout]
+                wk = wf.permute(2, 3, 0, 1) if tr else wf.permute(2, 3, 1, 0)
+                wk = wk.reshape(-1, wk.shape[2], wk.shape[3]).contiguous()
+                parts = []
+                step = 128 if wk.shape[2] % 128 == 0 else (64 if wk.shape[2] % 64 == 0 else 32)
+                for c0 in range(0, wk.shape[2], step):
+                    parts.append((c0, step, _sp3.pack_weight_f16(wk[:, :, c0:c0 + step].contiguous()), bf[c0:c0 + step].contiguous()))
+                levels.append(parts)
+            return levels
+        return derived(self, "amp_weights", build)
 
     def amp_ok(self, xs):
         plan, _ = self._plan()
@@ -644,10 +581,10 @@ class SecondFPN(_InferenceCache, nn.Module):
         plan, ctot = self._plan()
         n = int(xs[0].shape[0])
         out = None
-        tag = _param_signature(self)  # once per forward, not once per level
+        weights = self._amp_weights()
         for i, (p, x) in enumerate(zip(plan, xs)):
             h, w = int(x.shape[1]), int(x.shape[2])
-            (nbr, order, ho, wo), parts = self._amp_level(i, p, n, h, w, x.device, tag)
+            (nbr, order, ho, wo), parts = self._amp_level(i, n, h, w, x.device), weights[i]
             if out is None:
                 out = torch.empty((n, ho, wo, ctot), dtype=torch.float16, device=x.device)
             elif tuple(out.shape[1:3]) != (ho, wo):
@@ -716,7 +653,7 @@ class SeparateHead(nn.Module):
             getattr(self, "hm")[-1].bias.fill_(init_bias)
 
 
-class CenterHead(_InferenceCache, nn.Module):
+class CenterHead(InferenceCache, nn.Module):
     """center_head.py:156-220 forward + :294-339 predict_by_custom_op (inference only): BatchNorm folded, the 36
     first-stage 3x3 convolutions on the shared map run as ONE Winograd convolution, the 36 final convolutions as
     one grouped launch."""
@@ -740,7 +677,7 @@ class CenterHead(_InferenceCache, nn.Module):
             self.tasks.append(SeparateHead(share_conv_channel, heads, final_kernel=3, init_bias=init_bias))
 
     def _plan(self):
-        if not self._cache_valid():
+        def build():
             w0, b0 = _fold_conv_bn(self.shared_conv.conv, self.shared_conv.bn)
             ws, bs, plan, finals = [], [], [], []
             for t, task in enumerate(self.tasks):
@@ -762,11 +699,11 @@ class CenterHead(_InferenceCache, nn.Module):
             for g, (w, b) in enumerate(finals):
                 wf[g * cmax:g * cmax + w.shape[0]] = w
                 bf[g * cmax:g * cmax + w.shape[0]] = b
-            self._store_cache(dict(
+            return dict(
                 shared=_Conv3x3(w0, b0, 1), first=_Conv3x3(torch.cat(ws, 0).contiguous(), torch.cat(bs, 0).contiguous(), 1),
                 pf=_conv.pack_grouped_weight(wf, len(finals)), bf=bf, hc=int(hc), plan=plan, cmax=int(cmax), wf=wf,
-                groups=len(finals), ncls=[int(f[0].shape[0]) for f in finals]))
-        return self._cache
+                groups=len(finals), ncls=[int(f[0].shape[0]) for f in finals])
+        return derived(self, "plan", build)
 
     def forward(self, x, want_shared=True):
         """x [B, C, H, W] -> (per task dict of head maps, shared feature map), center_head.py:212-220.

@@ -16,6 +16,8 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from .derived import invalidate_derived
+
 __all__ = ["load_pdparams", "save_pdparams", "load_paddle_state_dict"]
 
 _STRUCT_KEY = "StructuredToParameterName@@"
@@ -88,11 +90,7 @@ def load_paddle_state_dict(model: nn.Module, state, strict: bool = True) -> list
             own[name].copy_(t)
             seen.add(name)
     unfilled = [k for k in own if k not in seen and not k.endswith("num_batches_tracked")]
-    for m in model.modules():  # derived (folded / packed) weights must be rebuilt
-        if hasattr(m, "_drop_cache"):
-            m._drop_cache()
-        if hasattr(m, "_folded"):
-            m._folded = None
+    invalidate_derived(model)
     if unplaced or unfilled:
         msg = (f"load_paddle_state_dict: {len(unplaced)} checkpoint keys without a place (e.g. {unplaced[:3]}), "
                f"{len(unfilled)} model entries without a value (e.g. {unfilled[:3]})")

@@ -34,6 +34,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .derived import derived
 from .ops import conv as conv_ops
 from .ops import dd3d as dd3d_ops
 
@@ -101,19 +102,18 @@ class _TowerConv(nn.Conv2d):
     """A tower's 3x3 convolution: torch's, or the F(4x4, 3x3) Winograd kernel on request (conv_kernel="winograd43")."""
 
     conv_kernel = "torch"
-    _packed = None
 
     def forward(self, x):
         b, cin, h, w = x.shape
         if (self.conv_kernel == "winograd43" and x.is_cuda and x.dtype == torch.float32 and
                 conv_ops.winograd43_supported(cin, self.out_channels, h, w)):
-            if self._packed is None or self._packed[0].device != x.device:
-                with torch.no_grad():
-                    bias = self.bias if self.bias is not None else torch.zeros(self.out_channels, device=x.device)
-                    self._packed = (conv_ops.pack_winograd43_weight(self.weight.float()), bias.float().contiguous())
+            def build():
+                bias = self.bias if self.bias is not None else torch.zeros(self.out_channels, device=x.device)
+                return conv_ops.pack_winograd43_weight(self.weight.float()), bias.float().contiguous()
+            packed = derived(self, "winograd43", build)
             pitch = conv_ops.pitch4(w)
             xp = x.contiguous() if pitch == w else F.pad(x, (0, pitch - w))
-            out = conv_ops.conv3x3_winograd43_bias_relu(xp, self._packed[0], self._packed[1], self.out_channels,
+            out = conv_ops.conv3x3_winograd43_bias_relu(xp, packed[0], packed[1], self.out_channels,
                                                         relu=False, w_valid=w)
             return out[:, :, :, :w]
         return super().forward(x)
@@ -486,10 +486,6 @@ class DD3D(nn.Module):
         self.register_buffer("pixel_mean", torch.tensor(pixel_mean, dtype=torch.float32).reshape(1, -1, 1, 1))
         self.register_buffer("pixel_std", torch.tensor(pixel_std, dtype=torch.float32).reshape(1, -1, 1, 1))
         self.input_strides, self.size_divisibility = list(input_strides), size_divisibility
-        self._packed = None
-
-    def _drop_cache(self):
-        self._packed = None
 
     def preprocess_image(self, x, size_divisibility=None):
         d = self.size_divisibility if size_divisibility is None else size_divisibility
@@ -583,31 +579,37 @@ class DD3D(nn.Module):
 
     def packed(self, device):
         """The lazy entry point's predictor arrays: box2d weight / bias, the stacked 3D predictors, the per-level scales."""
-        if self._packed is None or self._packed["scales"].device != device:
-            h2, h3 = self.fcos2d_head, self.fcos3d_head
-            L = len(self.input_strides)
-            with torch.no_grad():
-                scales = torch.ones((L, 6), dtype=torch.float32, device=device)
-                scales[:, 5] = 0
-                if h2.use_scale:
-                    scales[:, 0] = torch.cat([s.scale for s in h2.scales]).float()
-                p = dict(w2d=h2.box2d_reg.weight.float().contiguous(), b2d=h2.box2d_reg.bias.float().contiguous(),
-                         w3d=None, b3d=None, canon=None)
-                if h3 is not None:
-                    groups = (h3.box3d_quat, h3.box3d_ctr, h3.box3d_depth, h3.box3d_size, h3.box3d_conf)
-                    use = range(len(h3.box3d_quat)) if h3.use_per_level_predictors else (0,)
-                    p["w3d"] = torch.stack([torch.cat([g[i].weight for g in groups]) for i in use]).float().contiguous()
-                    p["b3d"] = torch.stack([torch.cat([g[i].bias if g[i].bias is not None else
-                                                       g[i].weight.new_zeros(g[i].weight.shape[0]) for g in groups])
-                                            for i in use]).float().contiguous()
-                    if h3.use_scale:
-                        for col, group in enumerate((h3.scales_proj_ctr, h3.scales_size, h3.scales_conf, h3.scales_depth), 1):
-                            scales[:, col] = torch.cat([s.scale for s in group]).float()[:L]
-                        scales[:, 5] = torch.cat([o.bias for o in h3.offsets_depth]).float()[:L]
-                    p["canon"] = torch.tensor(self.fcos3d_inference.canon_box_sizes, dtype=torch.float32, device=device)
-                p["scales"] = scales
-            self._packed = p
-        return self._packed
+        h2, h3 = self.fcos2d_head, self.fcos3d_head
+        L = len(self.input_strides)
+        # what build() reads and nothing more: a signature over `self` would walk the whole backbone on every forward
+        sources = [h2.box2d_reg, h2.scales if h2.use_scale else None]
+        if h3 is not None:
+            groups = (h3.box3d_quat, h3.box3d_ctr, h3.box3d_depth, h3.box3d_size, h3.box3d_conf)
+            sources += groups
+            if h3.use_scale:
+                sources += [h3.scales_proj_ctr, h3.scales_size, h3.scales_conf, h3.scales_depth, h3.offsets_depth]
+
+        def build():
+            scales = torch.ones((L, 6), dtype=torch.float32, device=device)
+            scales[:, 5] = 0
+            if h2.use_scale:
+                scales[:, 0] = torch.cat([s.scale for s in h2.scales]).float()
+            p = dict(w2d=h2.box2d_reg.weight.float().contiguous(), b2d=h2.box2d_reg.bias.float().contiguous(),
+                     w3d=None, b3d=None, canon=None)
+            if h3 is not None:
+                use = range(len(h3.box3d_quat)) if h3.use_per_level_predictors else (0,)
+                p["w3d"] = torch.stack([torch.cat([g[i].weight for g in groups]) for i in use]).float().contiguous()
+                p["b3d"] = torch.stack([torch.cat([g[i].bias if g[i].bias is not None else
+                                                   g[i].weight.new_zeros(g[i].weight.shape[0]) for g in groups])
+                                        for i in use]).float().contiguous()
+                if h3.use_scale:
+                    for col, group in enumerate((h3.scales_proj_ctr, h3.scales_size, h3.scales_conf, h3.scales_depth), 1):
+                        scales[:, col] = torch.cat([s.scale for s in group]).float()[:L]
+                    scales[:, 5] = torch.cat([o.bias for o in h3.offsets_depth]).float()[:L]
+                p["canon"] = torch.tensor(self.fcos3d_inference.canon_box_sizes, dtype=torch.float32, device=device)
+            p["scales"] = scales
+            return p
+        return derived(self, "packed", build, sources=sources, key=device)
 
     def tail_padded(self, cls_out, box_out, box3d_out, intrinsics=None, fused=None):
         """(rows [B, R, 20], counts int32 [B]) from the towers' outputs, no host synchronisation on the device paths.

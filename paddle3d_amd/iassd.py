@@ -22,6 +22,7 @@ import math
 
 import torch
 
+from .derived import derived
 from .ops import pointnet2_ops
 
 __all__ = ["QueryAndGroup", "sample_points", "SAModuleMSG_WithSampling", "Vote_layer", "IASSD_Backbone",
@@ -155,7 +156,6 @@ class SAModuleMSG_WithSampling(torch.nn.Module):
                 out_channels = confidence_mlp[k]
             layers.append(nn.Conv1d(out_channels, num_classes, 1, bias=True))
             self.confidence_layer = nn.Sequential(*layers)
-        self._folded = None
 
     def scale_is_fused(self, i, n=None):
         """Whether scale i runs as pd3_sa_msg_pool (on GPU tensors in eval mode) with n source points per frame."""
@@ -170,7 +170,7 @@ class SAModuleMSG_WithSampling(torch.nn.Module):
         return self.fused == "force" or (key in MEASURED_FASTER and (n is None or n <= MEASURED_FASTER[key]))
 
     def _fold(self):
-        if self._folded is None:
+        def build():
             scales = []
             for m in self.mlps:
                 if len(m) != 9:
@@ -181,11 +181,11 @@ class SAModuleMSG_WithSampling(torch.nn.Module):
                 for k in (3, 6):
                     p += [m[k].weight.detach().float().reshape(m[k].out_channels, -1).contiguous(), *_fold_bn(m[k + 1])]
                 scales.append(p)
-            self._folded = dict(
+            return dict(
                 scales=scales,
                 agg=None if self.aggregation_layer is None else _fold_stack(self.aggregation_layer),
                 conf=None if self.confidence_layer is None else _fold_stack(self.confidence_layer))
-        return self._folded
+        return derived(self, "folded", build, sources=(self.mlps, self.aggregation_layer, self.confidence_layer))
 
     def _unfused_scale(self, i, xyz, new_xyz, features):
         x = self.mlps[i](self.groupers[i](xyz, new_xyz, features))  # [B, C, npoint, nsample]
@@ -392,7 +392,6 @@ class IASSD_Head(torch.nn.Module):
         self.cls_center_layers = self.make_fc_layers(cls_fc, input_channel, num_classes)
         self.box_center_layers = self.make_fc_layers(reg_fc, input_channel, self.box_coder.code_size)
         self.forward_ret_dict = None
-        self._folded = None
 
     @staticmethod
     def make_fc_layers(fc_cfg, input_channel, output_channel):
@@ -406,13 +405,16 @@ class IASSD_Head(torch.nn.Module):
     def generate_predicted_boxes(self, points, point_cls_preds, point_box_preds):
         return point_cls_preds, self.box_coder.decode(point_box_preds, points, point_cls_preds)
 
+    def _fold(self):
+        stacks = (self.cls_center_layers, self.box_center_layers)
+        return derived(self, "folded", lambda: (_fold_stack(stacks[0]), _fold_stack(stacks[1])), sources=stacks)
+
     def forward(self, batch_dict):
         if self.training:
             raise NotImplementedError("IASSD_Head: inference only (no target assignment, no loss)")
         feats, centers = batch_dict["centers_features"], batch_dict["centers"]
-        if self._folded is None:
-            self._folded = (_fold_stack(self.cls_center_layers), _fold_stack(self.box_center_layers))
-        cls_preds, box_preds = _run_rows(self._folded[0], feats), _run_rows(self._folded[1], feats)
+        folded = self._fold()
+        cls_preds, box_preds = _run_rows(folded[0], feats), _run_rows(folded[1], feats)
         ret = {"center_cls_preds": cls_preds, "center_box_preds": box_preds}
         for k in ("ctr_offsets", "centers", "centers_origin", "sa_ins_preds"):
             ret[k] = batch_dict[k]

@@ -23,8 +23,8 @@ import torch
 import torch.nn as nn
 
 from ._lib import Paddle3DAmdError
-from .centerpoint import (HardVoxelizer, PillarFeatureNet, PointPillarsScatter, SecondBackbone, SecondFPN,
-                          _InferenceCache)
+from .centerpoint import HardVoxelizer, PillarFeatureNet, PointPillarsScatter, SecondBackbone, SecondFPN
+from .derived import InferenceCache, derived
 from .ops import conv as _conv
 from .ops import ssd_head as _ssd
 
@@ -88,7 +88,7 @@ class AnchorGenerator(nn.Module):
         self.anchor_area_threshold = float(anchor_area_threshold)
 
 
-class SSDHead(_InferenceCache, nn.Module):
+class SSDHead(InferenceCache, nn.Module):
     """pointpillars_head.py:31-196.  The modules hold the parameters (reference names cls_head / box_head / dir_head);
     forward runs the three 1x1 convolutions as one GEMM on the patch-GEMM kernel (bias fused, no activation)."""
 
@@ -116,15 +116,15 @@ class SSDHead(_InferenceCache, nn.Module):
             self.dir_head = nn.Conv2d(feature_channels, self.num_anchor_per_loc * 2, 1)
 
     def _plan(self):
-        if not self._cache_valid():
+        def build():
             heads = [self.cls_head, self.box_head] + ([self.dir_head] if self.use_direction_classifier else [])
             w = torch.cat([h.weight.detach() for h in heads], 0).contiguous()
             b = torch.cat([h.bias.detach() for h in heads], 0).contiguous()
             cls_c, box_c = self.cls_head.out_channels, self.box_head.out_channels
-            self._store_cache(dict(w=_conv.pack_patch_weight(w, 1, False), b=b, cout=int(w.shape[0]),
-                                   cin=int(w.shape[1]), cls0=0, box0=cls_c,
-                                   dir0=cls_c + box_c if self.use_direction_classifier else -1))
-        return self._cache
+            return dict(w=_conv.pack_patch_weight(w, 1, False), b=b, cout=int(w.shape[0]),
+                        cin=int(w.shape[1]), cls0=0, box0=cls_c,
+                        dir0=cls_c + box_c if self.use_direction_classifier else -1)
+        return derived(self, "plan", build)
 
     def head_map(self, features):
         """[B, C, H, W] -> the fused head map [B, cls | box | dir channels, H, W]."""

@@ -32,6 +32,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .derived import derived
 from .ops import conv as conv_ops
 from .ops import smoke as smoke_ops
 
@@ -178,10 +179,6 @@ class SMOKEPredictor(nn.Module):
         for m in self.regression_head:
             if isinstance(m, nn.Conv2d):
                 nn.init.constant_(m.bias, 0.0)
-        self._packed = None
-
-    def _drop_cache(self):
-        self._packed = None
 
     def forward(self, features, fused=None):
         if (self.fused if fused is None else fused) and features.is_cuda:
@@ -209,15 +206,14 @@ class SMOKEPredictor(nn.Module):
         winograd = self.conv_kernel == "winograd43" or (self.conv_kernel == "auto" and c >= WINOGRAD_MIN_WIDTH)
         if (winograd and features.is_cuda and features.dtype == torch.float32 and
                 conv_ops.winograd43_supported(cin, 2 * c, h, w)):
-            if self._packed is None or self._packed[0].device != features.device:
-                with torch.no_grad():
-                    weight = torch.cat([m.weight for m in convs]).float()
-                    self._packed = (conv_ops.pack_winograd43_weight(weight),
-                                    torch.cat([m.bias for m in convs]).float().contiguous())
+            def build():
+                weight = torch.cat([m.weight for m in convs]).float()
+                return (conv_ops.pack_winograd43_weight(weight),
+                        torch.cat([m.bias for m in convs]).float().contiguous())
+            packed = derived(self, "winograd43", build, sources=convs)
             pitch = conv_ops.pitch4(w)
             x = features.contiguous() if pitch == w else F.pad(features, (0, pitch - w))
-            out = conv_ops.conv3x3_winograd43_bias_relu(x, self._packed[0], self._packed[1], 2 * c, relu=False,
-                                                        w_valid=w)
+            out = conv_ops.conv3x3_winograd43_bias_relu(x, packed[0], packed[1], 2 * c, relu=False, w_valid=w)
             return out[:, :c, :, :w], out[:, c:, :, :w]
         return tuple(m(features) for m in convs)
 

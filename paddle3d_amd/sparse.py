@@ -10,6 +10,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from .derived import derived
 from .ops import sparse_conv3d as _sp
 
 __all__ = ["SparseConvTensor", "SubmConv3D", "Conv3D", "SparseBasicBlock", "SparseResNet3D", "SparseNet3D"]
@@ -95,23 +96,14 @@ class _SparseConv(nn.Module):
 
     out_f32 = False  # mixed precision: this convolution writes fp32 rows (an encoder's last layer, in front of to_dense)
 
-    def _packed_f16(self):
+    def _weight_f16(self):
         """The weight in the fp16 kernel's operand order, repacked when the parameter changes."""
-        tag = (self.weight.data_ptr(), self.weight._version, self.weight.device)
-        hit = getattr(self, "_pd3_packed", None)
-        if hit is None or hit[0] != tag:
-            hit = (tag, _sp.pack_weight_f16(self.weight.detach()))
-            object.__setattr__(self, "_pd3_packed", hit)
-        return hit[1]
+        return derived(self, "packed_f16", lambda: _sp.pack_weight_f16(self.weight.detach()), sources=self.weight)
 
-    def _packed_bf16x3(self):
+    def _weight_bf16x3(self):
         """The weight's three bf16 pieces in the bf16x3 kernel's operand order, repacked when the parameter changes."""
-        tag = (self.weight.data_ptr(), self.weight._version, self.weight.device)
-        hit = getattr(self, "_pd3_packed_x3", None)
-        if hit is None or hit[0] != tag:
-            hit = (tag, _sp.pack_weight_bf16x3(self.weight.detach()))
-            object.__setattr__(self, "_pd3_packed_x3", hit)
-        return hit[1]
+        return derived(self, "packed_bf16x3", lambda: _sp.pack_weight_bf16x3(self.weight.detach()),
+                       sources=self.weight)
 
     def forward(self, x: SparseConvTensor, scale=None, shift=None, residual=None, relu=False):
         idx = self._indices(x)
@@ -127,14 +119,14 @@ class _SparseConv(nn.Module):
             # fp16 rows in (converted once where the chain leaves the narrow fp32 layers), fp16 rows out
             feats = x.features if x.features.dtype == torch.float16 else x.features.half()
             res = residual if residual is None or residual.dtype == torch.float16 else residual.half()
-            out = _sp.features_f16(feats, idx, self._packed_f16(), cin, cout, self.bias, scale, shift, res, relu,
+            out = _sp.features_f16(feats, idx, self._weight_f16(), cin, cout, self.bias, scale, shift, res, relu,
                                    out_f32=self.out_f32)
         else:
             feats = x.features if x.features.dtype == torch.float32 else x.features.float()
             res = residual if residual is None or residual.dtype == torch.float32 else residual.float()
             if _sp.SPLIT_BF16 and _sp.bf16x3_pays(cin, cout, idx.kernel_volume):
                 # fp32 arithmetic on the bf16 matrix cores (three bf16 pieces per operand, six products)
-                out = _sp.features_bf16x3(feats, idx, self._packed_bf16x3(), cin, cout, self.bias, scale, shift, res,
+                out = _sp.features_bf16x3(feats, idx, self._weight_bf16x3(), cin, cout, self.bias, scale, shift, res,
                                           relu)
             else:
                 out = _sp.features(feats, idx, self.weight, self.bias, scale, shift, res, relu)
@@ -160,18 +152,13 @@ class Conv3D(_SparseConv):
 
 
 def _fold(bn: nn.BatchNorm1d):
-    """(scale, shift) of an eval-mode BatchNorm, computed once and kept on the module.  The cache entry is tied to
-    the identity AND the in-place version of the four tensors, so load_state_dict / .to() / an optimizer step all
-    invalidate it."""
-    src = (bn.weight, bn.bias, bn.running_mean, bn.running_var)
-    tag = tuple((t.data_ptr(), t._version, t.device) for t in src)
-    hit = getattr(bn, "_pd3_folded", None)
-    if hit is not None and hit[0] == tag:
-        return hit[1], hit[2]
-    scale = (bn.weight / torch.sqrt(bn.running_var + bn.eps)).detach().contiguous()
-    shift = (bn.bias - bn.running_mean * scale).detach().contiguous()
-    object.__setattr__(bn, "_pd3_folded", (tag, scale, shift))
-    return scale, shift
+    """(scale, shift) of an eval-mode BatchNorm, computed once and kept in a slot on the BatchNorm module itself
+    (derived.py), rebuilt when one of its four tensors changes."""
+    def build():
+        scale = (bn.weight / torch.sqrt(bn.running_var + bn.eps)).detach().contiguous()
+        shift = (bn.bias - bn.running_mean * scale).detach().contiguous()
+        return scale, shift
+    return derived(bn, "folded", build, sources=(bn.weight, bn.bias, bn.running_mean, bn.running_var))
 
 
 def _planned_input(encoder, voxel_features, coors, batch_size, caps=None):

@@ -12,8 +12,8 @@ SACISKBlock(num_channels, fused=True, conv3x3="auto")
     SAC_FUSED_MAX_CHANNELS (128: at C = 256 the kernel is slower than torch on one frame; fused="force" takes it there
     too); otherwise, and with fused=False, `sac_isk_composition`: the same formula as torch operators.  Both use the BatchNorms folded once after
     loading (scale = gamma / sqrt(var + eps), shift = (bias - mean) * scale + beta).
-conv3x3_bn_act(x, weight, scale, shift, act, kernel)
-    the helper every remaining 3x3 stride-1 layer goes through (the block's second MLP convolution, the decoder's):
+conv3x3_bn_act(layer, x, act, kernel)
+    the helper every remaining 3x3 stride-1 ConvBNLayer goes through (the block's second MLP convolution, the decoder's):
     `kernel` names a kernel of ops/conv.py ("direct", "winograd", "winograd43") taken when its *_supported predicate
     accepts the layer, else torch; "auto" is DEFAULT_CONV3X3's choice for the shape.
 The stride-(1, 2) downsample, the (1, 4) transposed convolution, the 1x1 layers and the bilinear resize of xyz
@@ -29,6 +29,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .derived import derived
 from .ops import conv as conv_ops
 from .ops import squeezeseg as ops
 
@@ -86,19 +87,19 @@ def conv3x3_kernel_for(kernel, cin, cout, h, w, device):
     return kernel if _CONV3X3_KERNELS[kernel][0](cin, cout, h, w) else "torch"
 
 
-def conv3x3_bn_act(x, weight, scale, shift, act="relu", kernel="auto", cache=None):
-    """act(BN(conv3x3(x))) for a stride-1, padding-1 layer with its BatchNorm folded into (scale, shift).  On a kernel
-    of ops/conv.py the scale goes into the weights (packed once into `cache`), the shift is the kernel's bias, relu is
-    the kernel's and a leaky relu follows it as a torch operator."""
+def conv3x3_bn_act(layer, x, act="relu", kernel="auto"):
+    """act(BN(conv3x3(x))) for a stride-1, padding-1 ConvBNLayer with its BatchNorm folded into (scale, shift).  On a
+    kernel of ops/conv.py the scale goes into the weights (packed once, kept on the layer in a slot named by the
+    kernel), the shift is the kernel's bias, relu is the kernel's and a leaky relu follows it as a torch operator."""
+    weight, (scale, shift) = layer._conv.weight, layer.folded()
     cout, cin = int(weight.shape[0]), int(weight.shape[1])
     name = conv3x3_kernel_for(kernel, cin, cout, int(x.shape[2]), int(x.shape[3]), x.device)
     if name == "torch":
         return _act(F.conv2d(x, weight, None, padding=1) * scale[None, :, None, None] + shift[None, :, None, None], act)
     _, pack, run = _CONV3X3_KERNELS[name]
-    cache = {} if cache is None else cache
-    if name not in cache:
-        cache[name] = pack((weight.double() * scale.double()[:, None, None, None]).float().contiguous())
-    y = run(x.contiguous(), cache[name], shift, cout, relu=(act == "relu"))
+    packed = derived(layer, name, sources=(weight, layer._batch_norm),
+                     build=lambda: pack((weight.double() * scale.double()[:, None, None, None]).float().contiguous()))
+    y = run(x.contiguous(), packed, shift, cout, relu=(act == "relu"))
     return y if act == "relu" else _act(y, act)
 
 
@@ -109,15 +110,13 @@ class ConvBNLayer(nn.Module):
         self._conv = nn.Conv2d(in_channels, out_channels, kernel_size, stride=_pair(stride), padding=_pair(padding),
                                bias=bias is not False)
         self._batch_norm = nn.BatchNorm2d(out_channels)
-        self._folded = None
 
     def folded(self):
-        """(scale, shift) float32 of the BatchNorm with the convolution's bias folded in, built once after loading."""
-        if self._folded is None:
-            bn = self._batch_norm
-            self._folded = ops.fold_batch_norm(bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps,
-                                               self._conv.bias)
-        return self._folded
+        """(scale, shift) float32 of the BatchNorm with the convolution's bias folded in, kept until either changes."""
+        bn = self._batch_norm
+        return derived(self, "folded", sources=(bn, self._conv.bias),
+                       build=lambda: ops.fold_batch_norm(bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps,
+                                                         self._conv.bias))
 
     def forward(self, x):
         bn = self._batch_norm
@@ -140,11 +139,6 @@ def _pair(v):
     return tuple(v) if isinstance(v, (list, tuple)) else (v, v)
 
 
-def _run_conv3x3(layer, x, act, kernel, cache):
-    scale, shift = layer.folded()
-    return conv3x3_bn_act(x, layer._conv.weight, scale, shift, act, kernel, cache)
-
-
 class SACISKBlock(nn.Module):
     """SAC-ISK.  forward(xyz, feature) -> (xyz, fused_feature)."""
 
@@ -157,26 +151,21 @@ class SACISKBlock(nn.Module):
         self.position_mlp = nn.Sequential(
             ConvBNLayer(9 * num_channels, num_channels, 1, bn_momentum=.9), nn.ReLU(),
             ConvBNLayer(num_channels, num_channels, 3, padding=1, bn_momentum=.9), nn.ReLU())
-        self._folded = None
-
-    def _drop_cache(self):
-        self._folded = None
-        for m in (self.attention_layer, self.position_mlp[0], self.position_mlp[2]):
-            m._folded = None
 
     def _params(self):
-        if self._folded is None:
+        att, mlp = self.attention_layer, self.position_mlp[0]
+
+        def build():
             C = self.num_channels
-            att, mlp = self.attention_layer, self.position_mlp[0]
             s_a, t_a = att.folded()
             s_m, t_m = mlp.folded()
             f = dict(w=att._conv.weight.detach(), s_a=s_a, t_a=t_a, v=mlp._conv.weight.detach().reshape(C, 9 * C),
-                     s_m=s_m, t_m=t_m, conv={})
+                     s_m=s_m, t_m=t_m)
             if ops.sac_isk_supported(C):
                 f["w1p"] = ops.pack_sac_attention_weight(f["w"])
                 f["w2p"] = ops.pack_sac_mlp_weight(f["v"])
-            self._folded = f
-        return self._folded
+            return f
+        return derived(self, "params", build, sources=(att, mlp))
 
     def takes_kernel(self, feature):
         N, C, H, W = feature.shape
@@ -197,7 +186,7 @@ class SACISKBlock(nn.Module):
 
     def forward(self, xyz, feature):
         y = self.first_layer(xyz, feature)
-        z = _run_conv3x3(self.position_mlp[2], y, "relu", self.conv3x3, self._params()["conv"])
+        z = conv3x3_bn_act(self.position_mlp[2], y, "relu", self.conv3x3)
         return xyz, z + feature
 
 
@@ -263,14 +252,10 @@ class InvertedResidual(nn.Module):
             nn.LeakyReLU(.1),
             ConvBNLayer(channels[0], channels[1], 3, stride=1, padding=1, bias=False, bn_momentum=bn_momentum),
             nn.LeakyReLU(.1))
-        self._cache = {}
-
-    def _drop_cache(self):
-        self._cache = {}
 
     def forward(self, x):
         y = self.conv[1](self.conv[0](x))
-        return _run_conv3x3(self.conv[2], y, "leaky", self.conv3x3, self._cache) + x
+        return conv3x3_bn_act(self.conv[2], y, "leaky", self.conv3x3) + x
 
 
 class DecoderStage(nn.Module):
@@ -286,16 +271,12 @@ class DecoderStage(nn.Module):
             self.layers.append(ConvBNLayer(in_channels, out_channels, 3, padding=1, bn_momentum=bn_momentum))
         self.layers.append(nn.LeakyReLU(.1))
         self.layers.append(InvertedResidual([in_channels, out_channels], bn_momentum=bn_momentum, conv3x3=conv3x3))
-        self._cache = {}
-
-    def _drop_cache(self):
-        self._cache = {}
 
     def forward(self, feature):
         if self.upsample:
             feature = self.layers[1](self.layers[0](feature))
         else:
-            feature = _run_conv3x3(self.layers[0], feature, "leaky", self.conv3x3, self._cache)
+            feature = conv3x3_bn_act(self.layers[0], feature, "leaky", self.conv3x3)
         return self.layers[2](feature)
 
 

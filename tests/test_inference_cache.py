@@ -1,39 +1,43 @@
-"""The derived-weight cache of the parameter-holding layers (paddle3d_amd/centerpoint.py: _InferenceCache,
-_param_signature, invalidate_derived): which writes it detects by itself, and the explicit invalidation for the one
+"""The derived-weight cache of the parameter-holding layers (paddle3d_amd/derived.py: signature, derived,
+invalidate_derived, InferenceCache): which writes it detects by itself, and the explicit invalidation for the one
 kind it cannot see (`param.data.*`)."""
 import pytest
 import torch
 
 from paddle3d_amd import centerpoint as cpm
+from paddle3d_amd import derived as dv
 
 
 def test_signature_sees_tensor_writes_but_not_data_writes():
     m = cpm.SecondBackbone(8, (8,), (1,), (2,)).eval()
     w = next(m.parameters())
-    s0 = cpm._param_signature(m)
+    s0 = dv.signature(m)
     with torch.no_grad():
         w.mul_(2.0)
-    s1 = cpm._param_signature(m)
+    s1 = dv.signature(m)
     assert s1 != s0                      # in-place op on the parameter: version bump
     w.data.mul_(2.0)
-    assert cpm._param_signature(m) == s1  # `.data` has a version counter of its own: invisible (documented)
+    assert dv.signature(m) == s1  # `.data` has a version counter of its own: invisible (documented)
     m.load_state_dict({k: v.clone() for k, v in m.state_dict().items()})
-    assert cpm._param_signature(m) != s1  # copy_ into the parameters
+    assert dv.signature(m) != s1  # copy_ into the parameters
+
+
+def _never():
+    raise AssertionError("the slot is valid: nothing to build")
 
 
 def test_invalidate_drops_every_derived_weight():
     model = cpm.centerpoint_pillars_nuscenes(max_num_voxels=(100, 100)).eval()
-    holders = [m for m in model.modules() if hasattr(m, "_drop_cache")]
+    holders = [m for m in model.modules() if isinstance(m, dv.InferenceCache)]
     assert len(holders) >= 3
-    for m in holders:
-        m._store_cache(("sentinel",))
-    model.voxel_encoder._folded = ("sig", ("sentinel",))
-    assert all(m._cache_valid() for m in holders)
+    for m in holders + [model.voxel_encoder]:
+        dv.derived(m, "plan", lambda: ("sentinel",))
+    assert all(dv.derived(m, "plan", _never) == ("sentinel",) for m in holders)  # valid: kept
     assert model.invalidate() is model
-    assert all(m._cache is None for m in holders) and model.voxel_encoder._folded is None
-    holders[0]._store_cache(("again",))
-    holders[0].invalidate()
-    assert holders[0]._cache is None
+    assert not any(dv.slots(m) for m in holders) and not dv.slots(model.voxel_encoder)
+    dv.derived(holders[0], "plan", lambda: ("again",))
+    assert holders[0].invalidate() is holders[0]
+    assert not dv.slots(holders[0])
 
 
 @pytest.mark.gpu

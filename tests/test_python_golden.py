@@ -250,8 +250,9 @@ def test_packed_weights_follow_in_place_and_child_updates():
     from paddle3d_amd import centerpoint as cpm
 
     head = cpm.centerpoint_pillars_nuscenes(max_num_voxels=(100, 100)).bbox_head.eval()
-    first = head._plan()["bf"].clone()
-    assert head._plan() is head._cache  # unchanged parameters: the same plan object
+    plan = head._plan()
+    first = plan["bf"].clone()
+    assert head._plan() is plan  # unchanged parameters: the same plan object
     task = head.tasks[0]
     name = list(task.heads)[0]
     with torch.no_grad():

@@ -184,7 +184,7 @@ def test_stacked_weight_is_rebuilt_after_a_load(golden):
     assert torch.equal(rows[:72], raw[:, :, 0, 0]) and not rows[72:].any()
     with torch.no_grad():
         head.conv_box.weight.mul_(2)  # an in-place write: seen through the version counter
-    assert not head._cache_valid()
+    assert head._stacked()[0] is not wp1  # the slot is not valid any more: rebuilt
 
 
 # ---- the models --------------------------------------------------------------------------------------------------------

@@ -102,12 +102,11 @@ def convs(a, dev, gen):
     for C, H, W in STAGES:
         torch.manual_seed(C)
         layer = randomise(sq.ConvBNLayer(C, C, 3, padding=1), C).to(dev).eval()
-        scale, shift = layer.folded()
         x = torch.randn(1, C, H, W, device=dev, generator=gen)
-        fns, cache = {}, {}
+        fns = {}
         for name in ("torch", "direct", "winograd", "winograd43"):
             if name == "torch" or sq.conv3x3_kernel_for(name, C, C, H, W, dev) == name:
-                fns[name] = lambda name=name: sq.conv3x3_bn_act(x, layer._conv.weight, scale, shift, "relu", name, cache)
+                fns[name] = lambda name=name: sq.conv3x3_bn_act(layer, x, "relu", name)
         want = fns["torch"]()
         for name, fn in fns.items():
             print(f"C = {C}: max |{name} - torch| = {float((fn() - want).abs().max()):.3g} (|max| {float(want.abs().max()):.3g})")
