@@ -31,8 +31,12 @@ def _block(scenarios, rows):
 
 
 def symbols(module=None):
-    """Every name of ENTRY_POINTS in table order, or those whose guarded scenarios live in tests/<module>.py."""
-    return tuple(name for name, row in ENTRY_POINTS.items() if module is None or row[2] == module)
+    """Every name of ENTRY_POINTS in table order, or those (of either table) whose guarded scenarios live in
+    tests/<module>.py."""
+    if module is None:
+        return tuple(ENTRY_POINTS)
+    return tuple(name for table in (ENTRY_POINTS, LANEDET_ENTRY_POINTS) for name, row in table.items()
+                 if row[2] == module)
 
 
 # the first models' ops: voxelization, pillar encoders, NMS, post-processing, point ops, sparse and dense convolutions
@@ -353,6 +357,18 @@ _block("test_memory_safety_dd3d_gpu", {
     "pd3_dd3d_post_process": (C.c_int, [C.c_void_p] * 11 + [C.c_int] * 4 + _DD3D_CFG),
 })
 
+# BEV-LaneDet's lane head tail and lane post-processing (csrc/lanedet.hip), declared in include/paddle3d_amd_lanedet.h.
+# A table of its own beside ENTRY_POINTS (whose size and blocks tests/test_abi.py pins), in the same row format;
+# tests/test_abi_lanedet.py holds it to its header, and symbols("test_memory_safety_lanedet_gpu") names its rows.
+_LANEDET_CFG = ([C.c_int] * 4 + [C.c_float] * 2 + [C.c_int] + [C.c_double] * 3 + [C.c_void_p] * 10 +
+                [C.c_size_t, C.c_void_p])  # batch .. stream
+LANEDET_ENTRY_POINTS = {name: row + ("test_memory_safety_lanedet_gpu",) for name, row in {
+    "pd3_lanedet_workspace": (C.c_size_t, [C.c_int] * 4),
+    "pd3_lanedet_post_process": (C.c_int, [C.c_void_p] * 4 + [C.c_int] + _LANEDET_CFG),
+    "pd3_lanedet_head_forward": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int, C.c_int] + [C.c_void_p] * 8 +
+                                 _LANEDET_CFG),
+}.items()}
+
 
 class Paddle3DAmdError(RuntimeError):
     pass
@@ -365,7 +381,7 @@ def lib() -> C.CDLL:
             f"{LIB_PATH} not found: build it with `python -m paddle3d_amd.build` "
             "(there is no CPU / PyTorch fallback for the HIP ops)")
     handle = C.CDLL(LIB_PATH)
-    for name, (res, args, _) in ENTRY_POINTS.items():
+    for name, (res, args, _) in [*ENTRY_POINTS.items(), *LANEDET_ENTRY_POINTS.items()]:
         try:
             fn = getattr(handle, name)
         except AttributeError as e:  # pragma: no cover
