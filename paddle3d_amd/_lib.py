@@ -31,12 +31,16 @@ def _block(scenarios, rows):
 
 
 def symbols(module=None):
-    """Every name of ENTRY_POINTS in table order, or those (of either table) whose guarded scenarios live in
+    """Every name of ENTRY_POINTS in table order, or those (of any table) whose guarded scenarios live in
     tests/<module>.py."""
     if module is None:
         return tuple(ENTRY_POINTS)
-    return tuple(name for table in (ENTRY_POINTS, LANEDET_ENTRY_POINTS) for name, row in table.items()
-                 if row[2] == module)
+    return tuple(name for table in _tables() for name, row in table.items() if row[2] == module)
+
+
+def _tables():
+    """ENTRY_POINTS and every side table, in the order they are bound."""
+    return (ENTRY_POINTS, *SIDE_TABLES)
 
 
 # the first models' ops: voxelization, pillar encoders, NMS, post-processing, point ops, sparse and dense convolutions
@@ -369,6 +373,16 @@ LANEDET_ENTRY_POINTS = {name: row + ("test_memory_safety_lanedet_gpu",) for name
                                  _LANEDET_CFG),
 }.items()}
 
+# CAPE / CAPE-T's cross-view attention core and 3D position embedding (csrc/cape.hip), declared in
+# include/paddle3d_amd_cape.h; tests/test_abi_cape.py holds the table to its header.
+CAPE_ENTRY_POINTS = {name: row + ("test_memory_safety_cape_gpu",) for name, row in {
+    "pd3_cape_cva_forward": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 6 + [C.c_void_p] * 2),
+    "pd3_cape_posemb3d": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_void_p] * 2),
+}.items()}
+
+# the tables beside ENTRY_POINTS, each with a header of its own: symbols(module) and lib() walk this tuple
+SIDE_TABLES = (LANEDET_ENTRY_POINTS, CAPE_ENTRY_POINTS)
+
 
 class Paddle3DAmdError(RuntimeError):
     pass
@@ -381,7 +395,7 @@ def lib() -> C.CDLL:
             f"{LIB_PATH} not found: build it with `python -m paddle3d_amd.build` "
             "(there is no CPU / PyTorch fallback for the HIP ops)")
     handle = C.CDLL(LIB_PATH)
-    for name, (res, args, _) in [*ENTRY_POINTS.items(), *LANEDET_ENTRY_POINTS.items()]:
+    for name, (res, args, _) in [row for table in _tables() for row in table.items()]:
         try:
             fn = getattr(handle, name)
         except AttributeError as e:  # pragma: no cover
