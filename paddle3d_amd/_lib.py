@@ -31,11 +31,11 @@ def _block(scenarios, rows):
 
 
 def symbols(module=None):
-    """Every name of ENTRY_POINTS in table order, or those (of any table) whose guarded scenarios live in
-    tests/<module>.py."""
+    """Every name of ENTRY_POINTS in table order, or those (of any table: _tables(), then LATER_TABLES) whose guarded
+    scenarios live in tests/<module>.py."""
     if module is None:
         return tuple(ENTRY_POINTS)
-    return tuple(name for table in _tables() for name, row in table.items() if row[2] == module)
+    return tuple(name for table in (*_tables(), *LATER_TABLES) for name, row in table.items() if row[2] == module)
 
 
 def _tables():
@@ -383,6 +383,17 @@ CAPE_ENTRY_POINTS = {name: row + ("test_memory_safety_cape_gpu",) for name, row 
 # the tables beside ENTRY_POINTS, each with a header of its own: symbols(module) and lib() walk this tuple
 SIDE_TABLES = (LANEDET_ENTRY_POINTS, CAPE_ENTRY_POINTS)
 
+# The modulated deformable convolution (csrc/deform_conv.hip), declared in include/paddle3d_amd_dcn.h;
+# tests/test_abi_dcn.py holds the table to its header.
+DCN_ENTRY_POINTS = {name: row + ("test_memory_safety_dcn_gpu",) for name, row in {
+    "pd3_deform_conv2d_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int,
+                                            C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 9 + [C.c_void_p] * 2),
+}.items()}
+
+# the tables added after SIDE_TABLES (which tests/test_abi_cape.py pins, as it pins _tables()): symbols(module) and lib()
+# walk this tuple after _tables()
+LATER_TABLES = (DCN_ENTRY_POINTS,)
+
 
 class Paddle3DAmdError(RuntimeError):
     pass
@@ -395,7 +406,7 @@ def lib() -> C.CDLL:
             f"{LIB_PATH} not found: build it with `python -m paddle3d_amd.build` "
             "(there is no CPU / PyTorch fallback for the HIP ops)")
     handle = C.CDLL(LIB_PATH)
-    for name, (res, args, _) in [row for table in _tables() for row in table.items()]:
+    for name, (res, args, _) in [row for table in (*_tables(), *LATER_TABLES) for row in table.items()]:
         try:
             fn = getattr(handle, name)
         except AttributeError as e:  # pragma: no cover

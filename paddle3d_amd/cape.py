@@ -582,12 +582,14 @@ def _cape_model(config, img_backbone, img_neck, fused):
 
 
 def cape_r50_1408x512(img_backbone=None, img_neck=None, fused=True):
-    """configs/cape/cape_r50_1408x512_24ep_wocbgs_imagenet_pretrain.yml behind the backbone and the neck."""
+    """configs/cape/cape_r50_1408x512_24ep_wocbgs_imagenet_pretrain.yml behind the backbone and the neck; the config's
+    backbone is paddle3d_amd.mm_resnet.mm_resnet50_caffe_dcn()."""
     return _cape_model("cape_r50_1408x512", img_backbone, img_neck, fused)
 
 
 def capet_r50_704x256(img_backbone=None, img_neck=None, fused=True):
-    """configs/cape/capet_r50_704x256_24ep_wocbgs_imagenet_pretrain.yml behind the backbone and the neck."""
+    """configs/cape/capet_r50_704x256_24ep_wocbgs_imagenet_pretrain.yml behind the backbone and the neck; the config's
+    backbone is paddle3d_amd.mm_resnet.mm_resnet50_caffe_dcn()."""
     return _cape_model("capet_r50_704x256", img_backbone, img_neck, fused)
 
 
