@@ -31,11 +31,12 @@ def _block(scenarios, rows):
 
 
 def symbols(module=None):
-    """Every name of ENTRY_POINTS in table order, or those (of any table: _tables(), then LATER_TABLES) whose guarded
-    scenarios live in tests/<module>.py."""
+    """Every name of ENTRY_POINTS in table order, or those (of any table: _tables(), then LATER_TABLES, then LAST_TABLES)
+    whose guarded scenarios live in tests/<module>.py."""
     if module is None:
         return tuple(ENTRY_POINTS)
-    return tuple(name for table in (*_tables(), *LATER_TABLES) for name, row in table.items() if row[2] == module)
+    return tuple(name for table in (*_tables(), *LATER_TABLES, *LAST_TABLES) for name, row in table.items()
+                 if row[2] == module)
 
 
 def _tables():
@@ -394,6 +395,17 @@ DCN_ENTRY_POINTS = {name: row + ("test_memory_safety_dcn_gpu",) for name, row in
 # walk this tuple after _tables()
 LATER_TABLES = (DCN_ENTRY_POINTS,)
 
+# BEVDepth's DepthNet: the ASPP and the softmax / channels-last tail (csrc/depthnet.hip), declared in
+# include/paddle3d_amd_depthnet.h; tests/test_abi_depthnet.py holds the table to its header.
+DEPTHNET_ENTRY_POINTS = {name: row + ("test_memory_safety_depthnet_gpu",) for name, row in {
+    "pd3_aspp_workspace": (C.c_size_t, [C.c_int] * 5),
+    "pd3_aspp_forward": (C.c_int, [C.c_void_p] * 11 + [C.c_int] * 8 + [C.c_void_p] * 2 + [C.c_size_t, C.c_void_p]),
+    "pd3_depth_softmax_split": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 3),
+}.items()}
+
+# the tables added after LATER_TABLES (which tests/test_abi_dcn.py pins): symbols(module) and lib() walk this tuple last
+LAST_TABLES = (DEPTHNET_ENTRY_POINTS,)
+
 
 class Paddle3DAmdError(RuntimeError):
     pass
@@ -406,7 +418,7 @@ def lib() -> C.CDLL:
             f"{LIB_PATH} not found: build it with `python -m paddle3d_amd.build` "
             "(there is no CPU / PyTorch fallback for the HIP ops)")
     handle = C.CDLL(LIB_PATH)
-    for name, (res, args, _) in [row for table in (*_tables(), *LATER_TABLES) for row in table.items()]:
+    for name, (res, args, _) in [row for table in (*_tables(), *LATER_TABLES, *LAST_TABLES) for row in table.items()]:
         try:
             fn = getattr(handle, name)
         except AttributeError as e:  # pragma: no cover

@@ -32,7 +32,8 @@ def _sources():
 def _headers():
     hs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")]
     hs.extend(os.path.join(HERE, "..", "include", h)
-              for h in ("paddle3d_amd.h", "paddle3d_amd_lanedet.h", "paddle3d_amd_cape.h", "paddle3d_amd_dcn.h"))
+              for h in ("paddle3d_amd.h", "paddle3d_amd_lanedet.h", "paddle3d_amd_cape.h", "paddle3d_amd_dcn.h",
+                        "paddle3d_amd_depthnet.h"))
     hs.append(os.path.abspath(__file__))  # the flags are in here
     return hs
 
